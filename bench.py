@@ -17,7 +17,14 @@ from the committed rocprofv3 PMC summary (profiles/) when it matches.
 cpu_baseline: the Eigen-free C restatement (oracle/, "port"), batched serial
 solves with OpenMP on the host cores, rank 0 only, bounded sample.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline value, the kernels' event times and the roofline they give).
+--dump-outputs DIR also writes the last timed step's output (dump_outputs).
+--full adds what takes runs of its own: the oracle check of the timed batch,
+the measured-copy and access-pattern probes, the end-to-end and secondary
+lines (C2, C3, wide, reuse, C5, C4) and the CPU baseline.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
  N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -952,6 +959,41 @@ def bench_end_to_end(bs, E, c, H, h, x0, ws0, out, dev, dist, local, steps=3, wa
                           "includes": "set_model H2D + update_problem_data + backward + forward + ws D2H"}}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # of w; the whole dump stays well under 64 MB
+
+
+def dump_outputs(path, out, status, rank=None):
+    """--dump-outputs: what a caller of the timed path holds after the last
+    timed step, as float64 .npy files under `path` (created if missing):
+      w.npy       the trajectories forward() wrote, one row per problem
+                  ([u_0 x_0 ... u_{N-1} x_{N-1} x_N], include/pdplqr.h); the
+                  whole batch when it fits the budget, else a fixed sample of
+                  problems (seed 0, ascending) -- or, when one trajectory alone
+                  exceeds it, problem 0 at a fixed sample of positions
+      w_rows.npy  the problem index of every row of w.npy
+      w_cols.npy  the position within the trajectory of every column of w.npy
+      status.npy  the per-problem factorisation status of the whole batch
+    The inputs are seeded (gen_batch_device), so two builds run with the same
+    arguments can be compared file for file.  Multi-rank runs append _rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    B, L = out.shape
+    rng = np.random.RandomState(0)
+    k = DUMP_BUDGET_BYTES // (8 * L)
+    if k >= B:
+        rows = np.arange(B)
+    elif k >= 1:
+        rows = np.sort(rng.choice(B, size=k, replace=False))
+    else:
+        rows = np.arange(1)
+    cols = np.arange(L) if k >= 1 else np.sort(rng.choice(L, size=DUMP_BUDGET_BYTES // 8, replace=False))
+    w = out[torch.as_tensor(rows, device=out.device)]
+    if cols.size < L:
+        w = w[:, torch.as_tensor(cols, device=out.device)]
+    sfx = "" if rank is None else f"_rank{rank}"
+    for name, a in (("w", w.cpu().numpy()), ("w_rows", rows), ("w_cols", cols), ("status", np.asarray(status))):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def bwd_kernel_name(n, m, keep):
     """The backward kernel the C ABI dispatches for this shape (kernels_schur.hip /
     kernels_riccati.hip launch_riccati_backward)."""
@@ -1014,7 +1056,15 @@ def main():
     ap.add_argument("--c4-N", type=int, default=65536)
     ap.add_argument("--secondary", default="all",
                     help="comma list of secondary lines (C2,C3,wide,reuse,C5,C4) or 'all'")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline value does not need: the oracle check of the timed batch, "
+                         "the copy and access-pattern probes, the end-to-end and secondary lines, the CPU baseline "
+                         "(--no-cpu, --no-secondary, --secondary, --cpu-seconds, --c4-N choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks here
@@ -1054,8 +1104,10 @@ def main():
     bs = BatchedLQRSolver(n, m, N, B, keep_factors=args.keep_factors, device=local)
     bs.set_model(E, c, H, h)
     # the handle holds its own copy; a sub-batch is kept for the host-memory (PCIe) line
-    Hk = H[:256].clone() if not args.no_secondary else None
-    Hk_full_sample = {b: H[b].cpu().numpy() for b in (0, B // 2, B - 1)}  # the oracle check's problems
+    secondary = args.full and not args.no_secondary
+    Hk = H[:256].clone() if secondary else None
+    # the oracle check's problems (--full)
+    Hk_full_sample = {b: H[b].cpu().numpy() for b in (0, B // 2, B - 1)} if args.full else None
     del H
     bs.update_problem_data(ws0, sigma=1e-6)
     bs.synchronize()
@@ -1087,12 +1139,16 @@ def main():
         dist.barrier()
     el = time.perf_counter() - t0
     st = bs.status()
-    # outside the timed region: the timed batch's output is finite and agrees
-    # with the CPU oracle on sampled problems (a wrong-but-finite answer would
-    # pass the status flags alone)
+    # outside the timed region: the timed batch's output is finite and, with
+    # --full, agrees with the CPU oracle on sampled problems (a wrong-but-finite
+    # answer would pass the status flags alone)
     finite = bool(torch.isfinite(out).all().item())
-    oracle_err = headline_oracle_err(E, c, Hk_full_sample, h, x0, out, n, m, N, (0, B // 2, B - 1))
-    status_ok = bool(np.all(st == 0)) and finite and oracle_err < 1e-9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, st, rank if world > 1 else None)
+    oracle_err = None
+    if args.full:
+        oracle_err = headline_oracle_err(E, c, Hk_full_sample, h, x0, out, n, m, N, (0, B // 2, B - 1))
+    status_ok = bool(np.all(st == 0)) and finite and (oracle_err is None or oracle_err < 1e-9)
     if dist:
         el = _max_over_ranks(dist, el, dev)
         status_ok = _max_over_ranks(dist, 0.0 if status_ok else 1.0, dev) == 0.0  # every rank's batch
@@ -1147,34 +1203,36 @@ def main():
         res["roofline"]["frac_moved"] = pmc["bytes_per_launch"] / (ms_bwd * 1e-3) / 1e9 / HBM_PEAK_GBS
         res["roofline"]["traffic_source"] = (f"committed PMC summary {pmc.get('_path', 'profiles/')}, same workload "
                                              "and kernel; not this run")
-    copy = measured_copy_gbs(dev)
-    copy_gbs = copy["float4"] or copy["blit"]
-    res["roofline"]["peak_measured_copy"] = copy_gbs
-    res["roofline"]["peak_measured_copy_blit"] = copy["blit"]
-    # fraction of the box's achievable copy rate the kernel uses: its moved
-    # (counter) bytes when a committed PMC summary exists, else algorithmic
-    moved = pmc["bytes_per_launch"] / (ms_bwd * 1e-3) / 1e9 if pmc else achieved
-    res["roofline"]["frac_of_measured_copy"] = moved / copy_gbs
-    res["roofline"]["frac_algorithmic_of_measured_copy"] = achieved / copy_gbs
-    res["roofline"]["note"] = ("achieved/frac count the SURVEY 8(d) algorithmic bytes (dense s x s H~); the kernel "
-                               "reads the packed H~ (s(s+1)/2 doubles), so it moves fewer bytes than that figure; "
-                               "frac_moved and frac_of_measured_copy use the counter bytes (peak_measured_copy: the "
-                               "16-byte streaming copy kernel, csrc/probe_pattern.hip; _blit: torch copy_)")
-    pat = pattern_ceiling_ms(dev, n, m, N, B)
-    if pat is not None:
-        # the kernels' own access pattern with nothing on the chain: the time
-        # their data flow needs on this box (1.0 = at that ceiling)
-        res["roofline"]["pattern_ceiling"] = {
-            "backward_ms": pat["backward"], "forward_ms": pat["forward"],
-            "backward_frac": pat["backward"] / ms_bwd, "forward_frac": pat["forward"] / ms_fwd,
-            "solve_frac": (pat["backward"] + pat["forward"]) / (ms_bwd + ms_fwd),
-            "probe": "csrc/probe_pattern.hip"}
-    if not args.no_secondary:
+    if args.full:  # the probes are runs of their own
+        copy = measured_copy_gbs(dev)
+        copy_gbs = copy["float4"] or copy["blit"]
+        res["roofline"]["peak_measured_copy"] = copy_gbs
+        res["roofline"]["peak_measured_copy_blit"] = copy["blit"]
+        # fraction of the box's achievable copy rate the kernel uses: its moved
+        # (counter) bytes when a committed PMC summary exists, else algorithmic
+        moved = pmc["bytes_per_launch"] / (ms_bwd * 1e-3) / 1e9 if pmc else achieved
+        res["roofline"]["frac_of_measured_copy"] = moved / copy_gbs
+        res["roofline"]["frac_algorithmic_of_measured_copy"] = achieved / copy_gbs
+        res["roofline"]["note"] = ("achieved/frac count the SURVEY 8(d) algorithmic bytes (dense s x s H~); the "
+                                   "kernel reads the packed H~ (s(s+1)/2 doubles), so it moves fewer bytes than that "
+                                   "figure; frac_moved and frac_of_measured_copy use the counter bytes "
+                                   "(peak_measured_copy: the 16-byte streaming copy kernel, csrc/probe_pattern.hip; "
+                                   "_blit: torch copy_)")
+        pat = pattern_ceiling_ms(dev, n, m, N, B)
+        if pat is not None:
+            # the kernels' own access pattern with nothing on the chain: the time
+            # their data flow needs on this box (1.0 = at that ceiling)
+            res["roofline"]["pattern_ceiling"] = {
+                "backward_ms": pat["backward"], "forward_ms": pat["forward"],
+                "backward_frac": pat["backward"] / ms_bwd, "forward_frac": pat["forward"] / ms_fwd,
+                "solve_frac": (pat["backward"] + pat["forward"]) / (ms_bwd + ms_fwd),
+                "probe": "csrc/probe_pattern.hip"}
+    if secondary:
         res["end_to_end"] = bench_end_to_end(bs, E, c, Hk, h, x0, ws0, out, dev, dist, local)
     bs.close()
     del E, c, h, x0, ws0, out, Hk
     torch.cuda.empty_cache()
-    if not args.no_secondary:
+    if secondary:
         lines = [("C2", "C2_single_N1024_parallel", lambda: bench_single(local, dev, dist, steps=50, warmup=5)),
                  ("C3", "C3_batched_N256", lambda: bench_batched_c3(local, dev, dist)),
                  ("wide", "wide_24x16_N256_b1024", lambda: bench_batched_c3(local, dev, dist, steps=5, warmup=2,
@@ -1184,11 +1242,11 @@ def main():
                  ("C4", "C4_horizon_sharded", lambda: bench_horizon(local, dev, dist, world, rank, args.c4_N, steps=10, warmup=2))]
         pick = None if args.secondary == "all" else set(args.secondary.split(","))
         res["secondary"] = {key: fn() for tag, key, fn in lines if pick is None or tag in pick}
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # rank 0 only, after every timed region (the other ranks are done)
         res["cpu_baseline"] = cpu_baseline(n, m, N, seconds=args.cpu_seconds)
     elif rank == 0:
-        res["cpu_baseline"] = None
+        res["cpu_baseline"] = None  # not measured
     assert res["n_gpus"] == args.gpus
     if rank == 0:
         print(json.dumps(res), flush=True)

@@ -12,7 +12,7 @@ TAG=${TAG:-N1024_n12_m4_b4096_kf0}
 DOM=${DOM:-k_riccati_bwd}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-if [ $# -eq 0 ]; then set -- python3 bench.py --steps 2 --warmup 1 --no-cpu --no-secondary; fi
+if [ $# -eq 0 ]; then set -- python3 bench.py --steps 2 --warmup 1; fi
 i=0
 for ctr in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_INSTS_SALU SQ_INSTS_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_MISC"; do
   i=$((i+1))

@@ -13,7 +13,7 @@
 #   py:<script args, comma separated>                    e.g. py:scripts/prof_c5.py
 #   trace:<script args, comma separated>                 rocprofv3 --kernel-trace --stats of that script
 #   rtrace:<script args, comma separated>                the same plus the HIP runtime API trace (host-side call times)
-#   bench:<bench.py args, comma separated>               e.g. bench:--no-cpu,--steps,20
+#   bench:<bench.py args, comma separated>               e.g. bench:--full,--no-cpu,--steps,20
 #   lat                                                  scripts/ubench/lat_bench
 #   pmc:<tag>,<dominant kernel>,<script args...>         PMC passes of one workload (scripts/collect_pmc.sh)
 #   env:NAME=VALUE / unenv:NAME                          set / clear an environment variable for the later steps
