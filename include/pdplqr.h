@@ -204,6 +204,25 @@ int pdplqr_clear_workspace(pdplqr_handle h);
  * SERIAL solver with keep_factors = 1 only.  Host outputs. */
 int pdplqr_get_value_function(pdplqr_handle h, int32_t b, int32_t k, double *P, double *p);
 
+/* Adjoint solve (new: the reference has no such call).  For a scalar loss l on
+ * the solution w* of the problem the handle last factored,
+ *     min sum 1/2 w_k^T H~_k w_k + h~_k^T w_k   s.t. x_{k+1} = E_k w_k + c_k, x_0 = x0
+ * (H~ = H + sigma I, h~ = h - sigma w of update_problem_data), writes
+ * dl/dE, dl/dc, dl/dH, dl/dh, dl/dx0 in the boundary layouts of E, c, H, h, x0,
+ * given `ws` (the solution the last forward returned) and `gws` = dl/dws
+ * ([batch][N*s + n]).  gH is the gradient with respect to the symmetric matrix
+ * (dl = <gH, dH> for symmetric dH; sigma does not enter it).  One
+ * backward_without_factorization and one forward on the cached factor give the
+ * adjoint solution, one streamed pass the gradients.
+ * Any output may be NULL: its work and traffic are skipped.  All non-NULL
+ * pointers live in `mem`.  SERIAL solver, keep_factors = 1, one device, no
+ * constraint rows, nx + nu <= 64 (PDPLQR_ERR_UNSUPPORTED otherwise); needs a
+ * preceding pdplqr_backward (PDPLQR_ERR_STATE).  The handle's state is
+ * unchanged: forward, backward_without_factorization and get_value_function
+ * behave as if the call had not happened. */
+int pdplqr_adjoint(pdplqr_handle h, const double *ws, const double *gws, double *gE, double *gc, double *gH,
+                   double *gh, double *gx, int mem);
+
 /* Per-problem factorization status after backward: 0 = ok, otherwise 1 + the
  * first stage whose Cholesky met a non-positive pivot (the reference ignores
  * Eigen's LLT info, lqr_kernel.hpp:89,126).  `flags` has `batch` entries, host. */

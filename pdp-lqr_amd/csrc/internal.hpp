@@ -120,6 +120,7 @@ int launch_riccati_forward(const Shape &sh, const double *E, const double *c, co
 namespace pdplqr { struct ParallelState;
 struct KKTState;
 struct AdmmState;
+struct AdjointState;
 struct MultiDev;
 // one slice of a num_devices split (multidev.hip)
 struct MdSlice {
@@ -171,6 +172,7 @@ struct pdplqr_handle_s {
     pdplqr::ParallelState *par = nullptr;  // PARALLEL solver state (solvers.hip)
     pdplqr::KKTState *kkt = nullptr;       // KKT solver state (kkt.hip)
     pdplqr::AdmmState *admm = nullptr;     // ADMM outer loop state (admm.hip), allocated on first use
+    pdplqr::AdjointState *adj = nullptr;   // pdplqr_adjoint scratch (adjoint.hip), allocated on first use
     int admm_iters = 0;                    // iterations of the last admm_solve
     int admm_rho_updates = 0;              // adaptive-rho refactorizations of the last admm_solve
     int shard_last = 1;  // last shard_backward's is_last_shard

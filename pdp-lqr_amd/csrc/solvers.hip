@@ -382,6 +382,7 @@ int solver_init(pdplqr_handle h) {
 void solver_release(pdplqr_handle h) {
     graph_release(h);
     admm_release(h);
+    adjoint_release(h);
     delete h->par;
     h->par = nullptr;
     kkt_release(h);

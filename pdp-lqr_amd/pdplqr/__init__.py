@@ -14,3 +14,13 @@ from .solvers import (  # noqa: F401
 from ._lib import LIB_PATH, PdplqrError, device_count, lib  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the torch layer (pdplqr/diff.py) is resolved on first use, so the package
+    # itself still imports without torch
+    if name == "LQRLayer":
+        from .diff import LQRLayer
+
+        return LQRLayer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -33,6 +33,7 @@ EXPORTS = [
     "pdplqr_shard_backward", "pdplqr_shard_backward_without_factorization", "pdplqr_shard_forward",
     "pdplqr_device_count",
     "pdplqr_admm_settings_init", "pdplqr_admm_solve", "pdplqr_admm_info", "pdplqr_multidev_plan",
+    "pdplqr_adjoint",
 ]
 
 
@@ -111,6 +112,8 @@ def lib() -> C.CDLL:
     L.pdplqr_admm_settings_init.restype = None
     L.pdplqr_admm_solve.argtypes = [vp, C.POINTER(AdmmSettings), dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.pdplqr_admm_info.argtypes = [vp, ip, ip, dp, dp, dp]
+    if hasattr(L, "pdplqr_adjoint"):  # (absent from older A/B variants)
+        L.pdplqr_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_multidev_plan"):  # (absent from pre-round-4 A/B variants)
         L.pdplqr_multidev_plan.argtypes = [i32, i32, ip, i32, i32, C.POINTER(C.c_int64)]
     for nm in EXPORTS:

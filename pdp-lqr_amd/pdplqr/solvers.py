@@ -202,6 +202,16 @@ class _Handle:
         check(lib().pdplqr_forward(self.h, ps[0][0], ps[1][0], _mem_of(*ps)))
         self._leave(cur)
 
+    def adjoint(self, ws, gws, gE=None, gc=None, gH=None, gh=None, gx=None):
+        """Gradients of a scalar loss with respect to E, c, H, h, x0 from
+        ``gws`` = d loss / d ws (include/pdplqr.h: pdplqr_adjoint).  Outputs
+        left ``None`` are not computed."""
+        objs = [ws, gws, gE, gc, gH, gh, gx]
+        ps = [_ptr(o, nm) for o, nm in zip(objs, ("ws", "gws", "gE", "gc", "gH", "gh", "gx"))]
+        cur = self._enter(*objs)
+        check(lib().pdplqr_adjoint(self.h, *[p[0] for p in ps], _mem_of(*ps)))
+        self._leave(cur)
+
     def clear_workspace(self):
         check(lib().pdplqr_clear_workspace(self.h))
 
@@ -454,6 +464,11 @@ class BatchedLQRSolver:
     def forward(self, x0, ws_out):
         self._hd.forward(x0, ws_out)
         return ws_out
+
+    def adjoint(self, ws, gws, gE=None, gc=None, gH=None, gh=None, gx=None):
+        """d loss / d (E, c, H, h, x0) from gws = d loss / d ws (serial solver,
+        keep_factors=True, after backward + forward); see pdplqr_adjoint."""
+        self._hd.adjoint(ws, gws, gE, gc, gH, gh, gx)
 
     def synchronize(self):
         self._hd.synchronize()
