@@ -223,6 +223,33 @@ int pdplqr_get_value_function(pdplqr_handle h, int32_t b, int32_t k, double *P, 
 int pdplqr_adjoint(pdplqr_handle h, const double *ws, const double *gws, double *gE, double *gc, double *gH,
                    double *gh, double *gx, int mem);
 
+/* The adjoint of the penalised x-update (new): pdplqr_adjoint for handles with
+ * constraint rows.  The handle last factored
+ *     H~_k = H_k + sigma I + D_k^T R D_k,   h~_k = h_k - sigma wbar_k - D_k^T R g_k
+ * with R = diag(rho) (the vector given to pdplqr_backward, passed again here;
+ * NULL only when no stage has rows) and g = zs - inv_rho o ys as
+ * update_problem_data left it; `ws` is the solution forward returned.  The loss
+ * may depend on the solution and on the rows' values:
+ *     gws = dl/dws [batch][N*s + n],  gvs = dl/d(D ws) [batch][sum nc_k] (NULL = 0),
+ * and the adjoint solve runs on the cached factor with the right-hand side
+ * gws + D^T gvs.  gE, gc, gH, gh, gx are as in pdplqr_adjoint (gH with respect
+ * to the model's H).  With r = D_k v_k (v the adjoint solution, = gh) and
+ * e = D_k w_k - g_k per row:
+ *     gD   [batch][sum nc_k*dim_k]  (rho o e) v_k^T + (rho o r + gvs_k) w_k^T, in D's layout
+ *     gg   [batch][sum nc_k]        -rho o r : the gradient of the penalty target g
+ *     grho [batch][sum nc_k]        r o e    : the gradient of rho with g held fixed
+ * The inputs of update_problem_data follow from these without further outputs:
+ *     dl/dzs = gg,  dl/dys = -inv_rho o gg,  dl/dinv_rho = -ys o gg,  dl/dwbar = -sigma gh.
+ * Any output may be NULL: its work and traffic are skipped.  Preconditions and
+ * the unchanged handle state are pdplqr_adjoint's, except that rows are allowed;
+ * without rows the results equal pdplqr_adjoint's bit for bit.  A stage whose rows
+ * do not fit the rows kernel's 40 KB LDS tile (32 bytes per row plus 16 (nx + nu))
+ * is PDPLQR_ERR_UNSUPPORTED.  A refused call
+ * writes nothing. */
+int pdplqr_adjoint_rows(pdplqr_handle h, const double *ws, const double *rho, const double *gws, const double *gvs,
+                        double *gE, double *gc, double *gH, double *gh, double *gx, double *gD, double *gg,
+                        double *grho, int mem);
+
 /* Per-problem factorization status after backward: 0 = ok, otherwise 1 + the
  * first stage whose Cholesky met a non-positive pivot (the reference ignores
  * Eigen's LLT info, lqr_kernel.hpp:89,126).  `flags` has `batch` entries, host. */

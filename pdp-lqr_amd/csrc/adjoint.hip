@@ -25,7 +25,9 @@ struct AdjointState {
     double *v = nullptr;                   // adjoint solution
     double *lpa = nullptr;                 // adjoint lp_k = [lu'; p^_k]
     double *lus = nullptr;                 // the primal lu'_k, [b][N][m]
-    double *out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // host outputs' staging (gE, gc, gH, gh, gx)
+    // host outputs' staging (gE, gc, gH, gh, gx, gD, gg, grho)
+    double *out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double *rho = nullptr, *gvs = nullptr;  // host rho / gvs staging (pdplqr_adjoint_rows)
 };
 
 void adjoint_release(pdplqr_handle h) {
@@ -71,45 +73,58 @@ static int fail(int code, const char *msg) {
 
 using namespace pdplqr;
 
-extern "C" int pdplqr_adjoint(pdplqr_handle h, const double *ws, const double *gws, double *gE, double *gc, double *gH,
-                              double *gh, double *gx, int mem) {
-    if (!h) return fail(PDPLQR_ERR_INVALID, "adjoint: null handle");
-    if (!ws || !gws) return fail(PDPLQR_ERR_INVALID, "adjoint: null ws/gws");
-    if (h->md) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint: multi-device handles are not supported");
-    if (h->cfg.solver != PDPLQR_SOLVER_SERIAL)
-        return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint needs a SERIAL handle (PARALLEL and KKT are not supported)");
-    if (h->sh.ny > 0) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint: constrained stages (ncs > 0) are not supported");
-    if (h->sh.s > 64) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint: n + m > 64 is not supported");
-    if (!h->cfg.keep_factors || !h->Lc || !h->lpc)
-        return fail(PDPLQR_ERR_STATE, "adjoint requires keep_factors = 1");
-    if (!h->factored) return fail(PDPLQR_ERR_STATE, "adjoint before backward");
-    if (h->rec_gain) return fail(PDPLQR_ERR_STATE, "adjoint: the rollout record is not in factor form");
-
+// The body of pdplqr_adjoint and pdplqr_adjoint_rows (`what` names the call in
+// messages).  The rows arguments (rho, gvs, gD, gg, grho) are all NULL for
+// pdplqr_adjoint, whose handles have no rows.
+static int adjoint_run(pdplqr_handle h, const char *what, const double *ws, const double *rho, const double *gws,
+                       const double *gvs, double *const user[8], int mem) {
     PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    const Shape &sh = h->sh;
+    AdjointRowsArgs ra;
+    if (sh.ny > 0 && !adjoint_rows_plan(sh, h->y_off_h.data(), h->d_off_h.data(), ra))
+        return fail(PDPLQR_ERR_UNSUPPORTED,
+                    (std::string(what) + ": the constraint rows of one stage exceed the kernel's LDS tile").c_str());
     int rc = adjoint_alloc(h);
     if (rc) return rc;
     AdjointState *s = h->adj;
-    const Shape &sh = h->sh;
     const long long B = sh.batch;
     const bool dev = mem == PDPLQR_MEM_DEVICE;
     hipStream_t st = h->stream;
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
 
     // inputs: ws is read in place on the device (host: staged as forward's output is);
-    // dl/dw is copied, so the recursion's kernel choice never depends on the caller's alignment
-    const double *dws = ws;
+    // the right-hand side is formed in the scratch buffer (a copy of dl/dw, or k_adjoint_rhs
+    // reading it), so the recursion's kernel choice never depends on the caller's alignment
+    const double *dws = ws, *drho = rho, *dgvs = gvs;
     if (!dev) {
         PDPLQR_HIP_TRY(hipMemcpyAsync(h->st_ws, ws, (size_t)(B * sh.perh) * sizeof(double), hipMemcpyHostToDevice, st));
         dws = h->st_ws;
+        if (sh.ny > 0) {
+            if (!s->rho && (rc = jalloc(h, &s->rho, B * sh.ny))) return rc;
+            PDPLQR_HIP_TRY(hipMemcpyAsync(s->rho, rho, (size_t)(B * sh.ny) * sizeof(double), in, st));
+            drho = s->rho;
+            if (gvs) {
+                if (!s->gvs && (rc = jalloc(h, &s->gvs, B * sh.ny))) return rc;
+                PDPLQR_HIP_TRY(hipMemcpyAsync(s->gvs, gvs, (size_t)(B * sh.ny) * sizeof(double), in, st));
+                dgvs = s->gvs;
+            }
+        }
     }
-    PDPLQR_HIP_TRY(hipMemcpyAsync(s->rhs, gws, (size_t)(B * sh.perh) * sizeof(double),
-                                  dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    // the adjoint solve's right-hand side: dl/dw (+ D^T dl/d(D w))
+    if (sh.ny > 0 && gvs && dev) {
+        if ((rc = launch_adjoint_rhs(sh, gws, dgvs, h->D, h->d_off, h->y_off, s->rhs, st))) return rc;
+    } else {
+        PDPLQR_HIP_TRY(hipMemcpyAsync(s->rhs, gws, (size_t)(B * sh.perh) * sizeof(double), in, st));
+        if (sh.ny > 0 && gvs && (rc = launch_adjoint_rhs(sh, s->rhs, dgvs, h->D, h->d_off, h->y_off, s->rhs, st)))
+            return rc;
+    }
     // outputs: the caller's device pointers, or staging allocated on first use
-    double *user[5] = {gE, gc, gH, gh, gx};
-    const long long cnt[5] = {B * sh.perE, B * sh.perc, B * sh.perH, B * sh.perh, B * sh.n};
-    double *out[5];
-    for (int i = 0; i < 5; ++i) {
-        out[i] = user[i];
-        if (user[i] && !dev) {
+    const long long cnt[8] = {B * sh.perE, B * sh.perc, B * sh.perH, B * sh.perh, B * sh.n,
+                              B * sh.ndD,  B * sh.ny,   B * sh.ny};
+    double *out[8];
+    for (int i = 0; i < 8; ++i) {
+        out[i] = cnt[i] > 0 ? user[i] : nullptr;
+        if (out[i] && !dev) {
             if (!s->out[i] && (rc = jalloc(h, &s->out[i], cnt[i]))) return rc;
             out[i] = s->out[i];
         }
@@ -148,15 +163,94 @@ extern "C" int pdplqr_adjoint(pdplqr_handle h, const double *ws, const double *g
     g.gh = out[3];
     g.gx = out[4];
     if ((rc = launch_adjoint_grad(g, st))) return rc;
+    if (out[5] || out[6] || out[7]) {
+        ra.ws = dws;
+        ra.v = s->v;
+        ra.D = h->D;
+        ra.rho = drho;
+        ra.g = h->gw;
+        ra.gvs = dgvs;
+        ra.d_off = h->d_off;
+        ra.y_off = h->y_off;
+        ra.gD = out[5];
+        ra.gg = out[6];
+        ra.grho = out[7];
+        if ((rc = launch_adjoint_rows(ra, h->y_off_h.data(), h->d_off_h.data(), st))) return rc;
+    }
 
     if (!dev) {
-        for (int i = 0; i < 5; ++i)
-            if (user[i])
+        for (int i = 0; i < 8; ++i)
+            if (out[i])
                 PDPLQR_HIP_TRY(hipMemcpyAsync(user[i], out[i], (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, st));
         PDPLQR_HIP_TRY(hipStreamSynchronize(st));
     }
     h->host_staged = false;
     return PDPLQR_OK;
+}
+
+extern "C" int pdplqr_adjoint(pdplqr_handle h, const double *ws, const double *gws, double *gE, double *gc, double *gH,
+                              double *gh, double *gx, int mem) {
+    if (!h) return fail(PDPLQR_ERR_INVALID, "adjoint: null handle");
+    if (!ws || !gws) return fail(PDPLQR_ERR_INVALID, "adjoint: null ws/gws");
+    if (h->md) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint: multi-device handles are not supported");
+    if (h->cfg.solver != PDPLQR_SOLVER_SERIAL)
+        return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint needs a SERIAL handle (PARALLEL and KKT are not supported)");
+    if (h->sh.ny > 0) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint: constrained stages (ncs > 0) are not supported");
+    if (h->sh.s > 64) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint: n + m > 64 is not supported");
+    if (!h->cfg.keep_factors || !h->Lc || !h->lpc)
+        return fail(PDPLQR_ERR_STATE, "adjoint requires keep_factors = 1");
+    if (!h->factored) return fail(PDPLQR_ERR_STATE, "adjoint before backward");
+    if (h->rec_gain) return fail(PDPLQR_ERR_STATE, "adjoint: the rollout record is not in factor form");
+    double *const user[8] = {gE, gc, gH, gh, gx, nullptr, nullptr, nullptr};
+    return adjoint_run(h, "adjoint", ws, nullptr, gws, nullptr, user, mem);
+}
+
+// The same with constraint rows: the handle last factored the penalised
+// x-update H~ = H + sigma I + D^T R D, h~ = h - sigma w - D^T R g (R = diag(rho),
+// g = h->gw from update_problem_data).  The penalty is inside the cached factor,
+// so the adjoint solve is the one above with the right-hand side gws + D^T gvs;
+// k_adjoint_rows (kernels_adjoint_rows.hip) adds the gradients of D, g and rho.
+extern "C" int pdplqr_adjoint_rows(pdplqr_handle h, const double *ws, const double *rho, const double *gws,
+                                   const double *gvs, double *gE, double *gc, double *gH, double *gh, double *gx,
+                                   double *gD, double *gg, double *grho, int mem) {
+    if (!h) return fail(PDPLQR_ERR_INVALID, "adjoint_rows: null handle");
+    if (!ws || !gws) return fail(PDPLQR_ERR_INVALID, "adjoint_rows: null ws/gws");
+    if (h->md) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint_rows: multi-device handles are not supported");
+    if (h->cfg.solver != PDPLQR_SOLVER_SERIAL)
+        return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint_rows needs a SERIAL handle (PARALLEL and KKT are not supported)");
+    if (h->sh.s > 64) return fail(PDPLQR_ERR_UNSUPPORTED, "adjoint_rows: n + m > 64 is not supported");
+    if (!h->cfg.keep_factors || !h->Lc || !h->lpc)
+        return fail(PDPLQR_ERR_STATE, "adjoint_rows requires keep_factors = 1");
+    if (!h->factored) return fail(PDPLQR_ERR_STATE, "adjoint_rows before backward");
+    if (h->rec_gain) return fail(PDPLQR_ERR_STATE, "adjoint_rows: the rollout record is not in factor form");
+    if (h->sh.ny > 0 && !rho) return fail(PDPLQR_ERR_INVALID, "adjoint_rows: null rho with constraint rows");
+    double *const user[8] = {gE, gc, gH, gh, gx, gD, gg, grho};
+    return adjoint_run(h, "adjoint_rows", ws, rho, gws, gvs, user, mem);
+}
+
+// Internal diagnostic (not part of include/pdplqr.h; scripts/adjoint_rows_bench.py):
+// the rows kernel alone, on the adjoint solution the last pdplqr_adjoint_rows
+// left in the scratch.  Device pointers; gvs may be NULL.
+extern "C" int pdplqr_debug_adjoint_rows(pdplqr_handle h, const double *ws, const double *rho, const double *gvs,
+                                         double *gD, double *gg, double *grho) {
+    if (!h || !ws || !rho || !h->adj || h->sh.ny == 0)
+        return fail(PDPLQR_ERR_STATE, "debug_adjoint_rows before adjoint_rows");
+    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    AdjointRowsArgs ra;
+    if (!adjoint_rows_plan(h->sh, h->y_off_h.data(), h->d_off_h.data(), ra))
+        return fail(PDPLQR_ERR_UNSUPPORTED, "debug_adjoint_rows: rows exceed the LDS tile");
+    ra.ws = ws;
+    ra.v = h->adj->v;
+    ra.D = h->D;
+    ra.rho = rho;
+    ra.g = h->gw;
+    ra.gvs = gvs;
+    ra.d_off = h->d_off;
+    ra.y_off = h->y_off;
+    ra.gD = gD;
+    ra.gg = gg;
+    ra.grho = grho;
+    return launch_adjoint_rows(ra, h->y_off_h.data(), h->d_off_h.data(), h->stream);
 }
 
 // Internal diagnostic (not part of include/pdplqr.h; scripts/adjoint_bench.py):

@@ -21,4 +21,22 @@ int launch_adjoint_lu(const Shape &sh, double *KD, double *buf, bool restore, hi
 size_t adjoint_lds_bytes(const Shape &sh, int ts);
 int adjoint_tile(const Shape &sh);
 
+// pdplqr_adjoint_rows: the gradients of the constraint rows (kernels_adjoint_rows.hip)
+struct AdjointRowsArgs {
+    Shape sh;
+    const double *ws, *v;             // primal and adjoint solutions [b][N*s + n]
+    const double *D, *rho, *g, *gvs;  // [b][ndD], [b][ny] each; gvs NULL = zero
+    const int32_t *d_off, *y_off;     // the handle's device tables (N + 2 entries)
+    double *gD, *gg, *grho;           // outputs; NULL = not wanted
+    int ts = 0, max_rows = 0;         // stages per block and the most rows of one tile (adjoint_rows_plan)
+    int lanes = 1;                    // lanes sharing one row's products, a power of two (adjoint_rows_plan)
+    int vecD = 0, vecY = 0;           // 16-byte stores allowed for gD / for gg and grho (set by the launcher)
+};
+// tile of the rows kernel from the host tables; false: one stage's rows do not fit the LDS tile
+bool adjoint_rows_plan(const Shape &sh, const int32_t *y_off_h, const int32_t *d_off_h, AdjointRowsArgs &a);
+int launch_adjoint_rows(const AdjointRowsArgs &a, const int32_t *y_off_h, const int32_t *d_off_h, hipStream_t st);
+// rhs = gws + D^T gvs (rhs may alias gws)
+int launch_adjoint_rhs(const Shape &sh, const double *gws, const double *gvs, const double *D, const int32_t *d_off,
+                       const int32_t *y_off, double *rhs, hipStream_t st);
+
 }  // namespace pdplqr

@@ -19,8 +19,8 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # the torch layer (pdplqr/diff.py) is resolved on first use, so the package
     # itself still imports without torch
-    if name == "LQRLayer":
-        from .diff import LQRLayer
+    if name in ("LQRLayer", "BoxLQRLayer"):
+        from . import diff
 
-        return LQRLayer
+        return getattr(diff, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

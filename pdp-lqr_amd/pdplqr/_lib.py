@@ -33,7 +33,7 @@ EXPORTS = [
     "pdplqr_shard_backward", "pdplqr_shard_backward_without_factorization", "pdplqr_shard_forward",
     "pdplqr_device_count",
     "pdplqr_admm_settings_init", "pdplqr_admm_solve", "pdplqr_admm_info", "pdplqr_multidev_plan",
-    "pdplqr_adjoint",
+    "pdplqr_adjoint", "pdplqr_adjoint_rows",
 ]
 
 
@@ -114,6 +114,8 @@ def lib() -> C.CDLL:
     L.pdplqr_admm_info.argtypes = [vp, ip, ip, dp, dp, dp]
     if hasattr(L, "pdplqr_adjoint"):  # (absent from older A/B variants)
         L.pdplqr_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
+    if hasattr(L, "pdplqr_adjoint_rows"):  # (absent from older A/B variants)
+        L.pdplqr_adjoint_rows.argtypes = [vp] + [dp] * 12 + [C.c_int]
     if hasattr(L, "pdplqr_multidev_plan"):  # (absent from pre-round-4 A/B variants)
         L.pdplqr_multidev_plan.argtypes = [i32, i32, ip, i32, i32, C.POINTER(C.c_int64)]
     for nm in EXPORTS:

@@ -12,6 +12,11 @@ of ``pdplqr_adjoint`` (an extra solve on the cached factor plus one streamed
 gradient pass), which writes only the gradients autograd asks for.  ``H`` is
 taken as symmetric; its gradient is the one with respect to the symmetric
 matrix.  There is no CPU path.
+
+``BoxLQRLayer`` (below) is the same for the box-constrained problem
+``lb <= D w <= ub`` solved by ``pdplqr_admm_solve``: its backward pass iterates
+the adjoint of one ADMM step at the solution, one ``pdplqr_adjoint_rows`` call
+on the cached factor per iteration.
 """
 from __future__ import annotations
 
@@ -79,6 +84,158 @@ class LQRLayer:
 
     def __call__(self, E, c, H, h, x0):
         return _LQRSolve.apply(self, E, c, H, h, x0)
+
+    @property
+    def handle(self) -> _Handle:
+        return self._hd
+
+    def close(self):
+        self._hd.close()
+
+
+class _BoxLQRSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, E, c, H, h, x0, D, lb, ub):
+        names = ("E", "c", "H", "h", "x0", "D", "lb", "ub")
+        ins = [layer._check(t, nm, cnt) for t, nm, cnt in zip((E, c, H, h, x0, D, lb, ub), names, layer._per)]
+        hd, rho = layer._hd, layer._rho
+        hd.set_model(*ins[:4], ins[5])
+        new = lambda cnt: torch.zeros(layer.batch, cnt, dtype=torch.float64, device=layer._dev)  # noqa: E731
+        ws, ys, zs = new(layer._per[3]), new(layer.ny), new(layer.ny)  # the zero start
+        hd.admm_solve(ins[4], ins[6], ins[7], rho, ws, ys, zs, layer._settings)
+        layer.admm_info = hd.admm_info()
+        # one protocol x-update at the returned (w*, y*, z*): the handle's factor, g and
+        # lp now belong to the fixed point, whatever path admm_solve's last iteration took
+        hd.update_problem_data(ws, ys, zs, layer._irho, layer.sigma)
+        hd.backward(rho)
+        wt = torch.empty_like(ws)
+        hd.forward(ins[4], wt)
+        layer._gen += 1  # the handle now holds THIS call's factorization
+        ctx.layer, ctx.gen = layer, layer._gen
+        ctx.converged = bool(layer.admm_info["converged"].all())
+        ctx.shapes = [t.shape for t in (E, c, H, h, x0, D, lb, ub)]
+        ctx.save_for_backward(wt, ys, zs, ins[6], ins[7])
+        return ws
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gws):
+        layer = ctx.layer
+        if ctx.gen != layer._gen:
+            raise RuntimeError(
+                "BoxLQRLayer: backward through a solution whose factorization is gone: the layer was called again "
+                f"(call {layer._gen}) after the call being differentiated (call {ctx.gen}), and its handle keeps "
+                "one factorization.  Call backward before the next forward, or use one BoxLQRLayer per live graph.")
+        if not ctx.converged and not layer.allow_unconverged:
+            raise RuntimeError(
+                "BoxLQRLayer: the ADMM solve being differentiated did not converge for every problem of the batch "
+                "(layer.admm_info); the fixed-point adjoint is meaningless there.  Raise max_iter, loosen eps, or "
+                "build the layer with allow_unconverged=True.")
+        wt, ys, zs, lb, ub = ctx.saved_tensors
+        hd, rho, al, sg = layer._hd, layer._rho, layer.alpha, layer.sigma
+        tt = zs + ys / rho
+        at_lb, at_ub = tt <= lb, tt >= ub
+        M = (~(at_lb | at_ub)).to(torch.float64)
+        gws = gws.contiguous()
+        a_w, a_y, a_z = torch.zeros_like(gws), torch.zeros_like(ys), torch.zeros_like(ys)
+        gh, gg = torch.empty_like(gws), torch.empty_like(ys)
+
+        def cotangents():
+            b_w = gws + a_w
+            q = a_z - rho * a_y
+            return b_w, q, rho * a_y + M * q
+
+        # a <- dl/ds + J^T a through one ADMM step at the fixed point s = (w, y, z)
+        layer.adjoint_iterations = 0
+        for it in range(1, layer.adj_max_iter + 1):
+            b_w, q, b_vr = cotangents()
+            hd.adjoint_rows(wt, rho, al * b_w, al * b_vr, gh=gh, gg=gg)
+            n_w = (1.0 - al) * b_w - sg * gh
+            n_y = a_y + M * q / rho - gg / rho
+            n_z = (1.0 - al) * b_vr + gg
+            test = it % layer.check_every == 0 or it == layer.adj_max_iter
+            if test:  # per problem: max-norm change <= adj_tol * max-norm
+                ch = torch.cat([(n_w - a_w).abs(), (n_y - a_y).abs(), (n_z - a_z).abs()], dim=1).amax(dim=1)
+                nrm = torch.cat([n_w.abs(), n_y.abs(), n_z.abs()], dim=1).amax(dim=1)
+            a_w, a_y, a_z = n_w, n_y, n_z
+            layer.adjoint_iterations = it
+            if test and bool((ch <= layer.adj_tol * nrm).all().item()):
+                break
+
+        b_w, q, b_vr = cotangents()
+        need = ctx.needs_input_grad[1:]
+        outs = [torch.empty(layer.batch, cnt, dtype=torch.float64, device=layer._dev) if nd else None
+                for cnt, nd in zip(layer._per[:6], need[:6])]
+        if any(o is not None for o in outs):
+            hd.adjoint_rows(wt, rho, al * b_w, al * b_vr, *outs)
+        outs.append(q * at_lb if need[6] else None)
+        outs.append(q * at_ub if need[7] else None)
+        return (None,) + tuple(o.view(shp) if o is not None else None for o, shp in zip(outs, ctx.shapes))
+
+
+class BoxLQRLayer:
+    """``ws = layer(E, c, H, h, x0, D, lb, ub)``: the optimum of
+
+        min sum 1/2 w_k^T H_k w_k + h_k^T w_k
+        s.t. x_{k+1} = E_k w_k + c_k,  x_0 = x0,  lb <= D w <= ub
+
+    by ``pdplqr_admm_solve`` from a zero start (rows per stage ``ncs``, N + 1
+    counts), differentiable once in all eight inputs (float64 CUDA tensors in
+    the boundary layout of include/pdplqr.h).
+
+    ``rho`` (a number, or ``[batch][ny]`` values) is fixed: adaptive rho is off,
+    the backward pass assumes the rho the solve ended with.  ``eps`` is the
+    absolute tolerance of the ADMM residuals (``eps_rel`` = 0).  ``backward`` is
+    a fixed-point adjoint iteration through one ADMM step at the solution, one
+    ``pdplqr_adjoint_rows`` call on the cached factor per iteration, until the
+    max-norm change of the adjoint state is at most ``adj_tol`` times its
+    max-norm for every problem (tested every ``check_every`` iterations with one
+    small device-to-host read) or ``adj_max_iter`` is reached; it needs about
+    as many iterations as the forward solve.  The gradients are those of the
+    optimum when it is strictly complementary.  ``backward`` raises
+    ``RuntimeError`` if a problem did not converge (unless
+    ``allow_unconverged``), or if the layer was called again in between (the
+    handle keeps ONE factorization).  ``admm_info`` holds the last solve's
+    outcome, ``adjoint_iterations`` the last backward's count."""
+
+    def __init__(self, n: int, m: int, N: int, batch: int, ncs, rho, sigma: float = 1e-6, alpha: float = 1.6,
+                 eps: float = 1e-6, max_iter: int = 4000, adj_tol: float = 1e-8, adj_max_iter: int = 4000,
+                 check_every: int = 25, allow_unconverged: bool = False, device: int = 0):
+        from .solvers import admm_settings
+
+        self.n, self.m, self.N, self.batch = int(n), int(m), int(N), int(batch)
+        self.sigma, self.alpha = float(sigma), float(alpha)
+        self.adj_tol, self.adj_max_iter, self.check_every = float(adj_tol), int(adj_max_iter), int(check_every)
+        self.allow_unconverged = bool(allow_unconverged)
+        s = n + m
+        ncs = [int(x) for x in ncs]
+        if len(ncs) != N + 1:
+            raise ValueError("BoxLQRLayer: ncs needs N + 1 entries")
+        self.ny = sum(ncs)
+        if self.ny == 0:
+            raise ValueError("BoxLQRLayer: no constraint rows (use LQRLayer)")
+        ndD = sum(nc * (s if k < N else n) for k, nc in enumerate(ncs))
+        # doubles per problem of E, c, H, h (= ws), x0, D, lb, ub
+        self._per = (N * n * s, N * n, N * s * s + n * n, N * s + n, n, ndD, self.ny, self.ny)
+        self._dev = torch.device("cuda", int(device))
+        self._hd = _Handle(n, m, N, batch, _lib.PDPLQR_SOLVER_SERIAL, device=device, keep_factors=True, ncs=ncs)
+        rho = torch.as_tensor(rho, dtype=torch.float64).detach().to(self._dev)
+        self._rho = (rho.expand(batch, self.ny) if rho.numel() == 1 else rho.reshape(batch, self.ny)).contiguous()
+        self._irho = (1.0 / self._rho).contiguous()
+        self._settings = admm_settings(sigma, alpha, max_iter, check_every, eps, 0.0, False)
+        self._gen = 0
+        self.admm_info = None
+        self.adjoint_iterations = 0
+
+    def _check(self, t, name, per):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self._dev:
+            raise TypeError(f"BoxLQRLayer: {name} must be a float64 tensor on {self._dev}")
+        if t.numel() != self.batch * per:
+            raise ValueError(f"BoxLQRLayer: {name} has {t.numel()} entries, expected batch * {per}")
+        return t.detach().contiguous().view(self.batch, per)
+
+    def __call__(self, E, c, H, h, x0, D, lb, ub):
+        return _BoxLQRSolve.apply(self, E, c, H, h, x0, D, lb, ub)
 
     @property
     def handle(self) -> _Handle:

@@ -212,6 +212,19 @@ class _Handle:
         check(lib().pdplqr_adjoint(self.h, *[p[0] for p in ps], _mem_of(*ps)))
         self._leave(cur)
 
+    def adjoint_rows(self, ws, rho, gws, gvs=None, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, gg=None,
+                     grho=None):
+        """``adjoint`` for a handle with constraint rows (include/pdplqr.h:
+        pdplqr_adjoint_rows): ``rho`` as given to ``backward``, ``gvs`` =
+        d loss / d (D ws) or ``None``; adds the gradients of ``D``, of the
+        penalty target ``g`` and of ``rho``."""
+        objs = [ws, rho, gws, gvs, gE, gc, gH, gh, gx, gD, gg, grho]
+        names = ("ws", "rho", "gws", "gvs", "gE", "gc", "gH", "gh", "gx", "gD", "gg", "grho")
+        ps = [_ptr(o, nm) for o, nm in zip(objs, names)]
+        cur = self._enter(*objs)
+        check(lib().pdplqr_adjoint_rows(self.h, *[p[0] for p in ps], _mem_of(*ps)))
+        self._leave(cur)
+
     def clear_workspace(self):
         check(lib().pdplqr_clear_workspace(self.h))
 
@@ -469,6 +482,12 @@ class BatchedLQRSolver:
         """d loss / d (E, c, H, h, x0) from gws = d loss / d ws (serial solver,
         keep_factors=True, after backward + forward); see pdplqr_adjoint."""
         self._hd.adjoint(ws, gws, gE, gc, gH, gh, gx)
+
+    def adjoint_rows(self, ws, rho, gws, gvs=None, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, gg=None,
+                     grho=None):
+        """The same after a penalised x-update (``ncs`` > 0): also d loss /
+        d (D, g, rho), with ``gvs`` = d loss / d (D ws); see pdplqr_adjoint_rows."""
+        self._hd.adjoint_rows(ws, rho, gws, gvs, gE, gc, gH, gh, gx, gD, gg, grho)
 
     def synchronize(self):
         self._hd.synchronize()
