@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define PDPLQR_VERSION_MAJOR 0
-#define PDPLQR_VERSION_MINOR 1
+#define PDPLQR_VERSION_MINOR 2
 
 /* status codes */
 #define PDPLQR_OK 0
@@ -329,6 +329,70 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *s, const doub
 /* batch (>= 1) or an error code.                                             */
 int pdplqr_admm_info(pdplqr_handle h, int32_t *iters, int32_t *converged, double *prim_res, double *dual_res,
                      double *rho);
+
+/* ---------------------------------------------------------------------- */
+/* Infeasibility detection of the ADMM loop (new; OSQP's certificates,     */
+/* Stellato et al. 2020 section 3.4, in the coordinates of the dynamics'    */
+/* affine set -- the x-update solves the dynamics exactly).  */
+/* A problem whose feasible set {w : dynamics, lb <= D w <= ub} is empty,   */
+/* or whose cost is unbounded below on it, is recognised at a termination   */
+/* test, frozen like a converged one and reported by pdplqr_admm_status.    */
+/* Limits: SERIAL and PARALLEL handles on one device (num_devices 0 or 1    */
+/* without `devices`), nx + nu <= 64, any ncs, either keep_factors value;   */
+/* PDPLQR_ERR_UNSUPPORTED otherwise (the KKT solver softens its dynamics by */
+/* rho_dyn, so "infeasible" is not the same statement there).  A small rho  */
+/* or a long unstable horizon (nu grows with |A^T|^N) certifies slowly.     */
+/* ---------------------------------------------------------------------- */
+#define PDPLQR_ADMM_UNSOLVED 0          /* ran to max_iter                       */
+#define PDPLQR_ADMM_SOLVED 1            /* the termination test passed           */
+#define PDPLQR_ADMM_PRIMAL_INFEASIBLE 2 /* no feasible point                     */
+#define PDPLQR_ADMM_DUAL_INFEASIBLE 3   /* cost unbounded below                  */
+
+/* Detection state of the handle (default: off; with it off admm_solve        */
+/* launches and copies nothing new and its results are unchanged bit for bit). */
+/* eps_prim_inf / eps_dual_inf: OSQP's defaults are 1e-4; a tolerance of 0     */
+/* switches that one test off; negative or NaN with `enable` set is            */
+/* PDPLQR_ERR_INVALID.  With dy = y^{k+1} - y^k, dw = w^{k+1} - w^k at a       */
+/* termination test and |.| the max-norm, a bound with |value| >= 1e20 being   */
+/* infinite:                                                                   */
+/*   primal: nu_N = q_N, [g_k; nu_k] = q_k + E_k^T nu_{k+1} with q_k = D_k^T   */
+/*     dy_k, beta = sum_k nu_{k+1}^T c_k + nu_0^T x0; certified when |dy| > 0, */
+/*     max_k |g_k| <= eps |dy|, no row has dy_i > eps |dy| with ub_i infinite  */
+/*     or dy_i < -eps |dy| with lb_i infinite, and                             */
+/*     sum_i [ub_i (dy_i)+ + lb_i (dy_i)-] - beta < -eps |dy| (finite bounds); */
+/*   dual: certified when |dw| > 0, |H_k dw_k| <= eps |dw| for all k (the      */
+/*     model's H, without sigma), sum_k h_k^T dw_k < -eps |dw|, |dx_0| and     */
+/*     |dx_{k+1} - E_k dw_k| <= eps |dw|, and for every row (D dw)_i <= eps    */
+/*     |dw| where ub_i is finite, >= -eps |dw| where lb_i is finite.           */
+/* A problem that passes the termination test in the same pass is SOLVED.     */
+int pdplqr_admm_set_infeasibility_detection(pdplqr_handle h, int enable, double eps_prim_inf, double eps_dual_inf);
+
+/* PDPLQR_ADMM_* of every problem after the last admm_solve (host array of    */
+/* `batch` entries).  With detection off only 0 and 1 occur and the value     */
+/* equals `converged` of pdplqr_admm_info.  PDPLQR_ERR_STATE before any       */
+/* admm_solve.                                                                 */
+int pdplqr_admm_status(pdplqr_handle h, int32_t *status);
+
+/* The certificates of the last admm_solve: dy [batch][ny], dw [batch][N*s+n] */
+/* (either may be NULL), both in `mem`.  A problem with status 2 or 3 gets    */
+/* the dy / dw of the deciding test, every other problem zeros.               */
+/* PDPLQR_ERR_STATE unless detection was on in the last admm_solve.           */
+int pdplqr_admm_certificate(pdplqr_handle h, double *dy, double *dw, int mem);
+
+/* The two certificate tests on given vectors, without the loop: needs only   */
+/* set_model, same limits as above; changes no handle state.  x0 [batch][n],  */
+/* lb, ub, dy [batch][ny], dw [batch][N*s+n], all pointers in `mem`.          */
+/* measures [batch][8]:                                                        */
+/*   [0] |dy|   [1] max_k |g_k|   [2] the support term (the sum minus beta)   */
+/*   [3] 1 if a row with an infinite bound fails the sign test, else 0        */
+/*   [4] |dw|   [5] max_k |H_k dw_k|   [6] h^T dw                             */
+/*   [7] max of the dynamics residuals (dx_0 included) and the row violations */
+/* verdict [batch]: bit 0 = primal certificate holds, bit 1 = dual.  dy or dw */
+/* NULL skips that half (its measures are 0, its bit clear; lb, ub may then   */
+/* be NULL only when no stage has rows).                                       */
+int pdplqr_admm_check_certificates(pdplqr_handle h, const double *x0, const double *lb, const double *ub,
+                                   const double *dy, const double *dw, double eps_prim_inf,
+                                   double eps_dual_inf, double *measures, int32_t *verdict, int mem);
 
 /* Device info helpers (for hosts that do not link HIP). */
 int pdplqr_device_count(int32_t *count);

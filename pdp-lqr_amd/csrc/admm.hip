@@ -63,6 +63,12 @@ struct AdmmState {
     int32_t *done = nullptr, *iters = nullptr, *conv = nullptr;
     int32_t *active = nullptr;    // [0] problems still iterating, [1] some rho changed
     int32_t *active_h = nullptr;  // pinned copy of active[0..1]
+    // infeasibility detection (allocated by the first admm_solve that runs with it on)
+    double *yp = nullptr, *wp = nullptr;  // (y, w) before the update pass of the last test iteration
+    double *meas = nullptr;               // [b][8] measures of the last test
+    int32_t *istat = nullptr;             // [b] 0, or PDPLQR_ADMM_{PRIMAL,DUAL}_INFEASIBLE
+    bool solved_once = false;             // an admm_solve ran its loop
+    bool detect_last = false;             // the last admm_solve ran with detection on
 };
 
 // sum over the LPS lanes of one stage (xor butterflies: every lane ends with
@@ -603,8 +609,81 @@ static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const 
     PDPLQR_HIP_TRY(hipStreamSynchronize(S));
     h->admm_iters = it;
     h->admm_rho_updates = rho_updates;
+    s->solved_once = true;
+    s->detect_last = false;
     return PDPLQR_OK;
 }
+
+// the uniform row layout of AdmmArgs::uni: c0 > 0 rows at every stage k < N, none at the terminal
+static int uniform_rows(pdplqr_handle h) {
+    const Shape &sh = h->sh;
+    const int c0 = sh.N > 0 ? h->ncs[0] : 0;
+    bool uni = c0 > 0 && h->ncs[sh.N] == 0;
+    for (int k = 0; k < sh.N && uni; ++k) uni = h->ncs[k] == c0;
+    return uni ? c0 : 0;
+}
+
+// why infeasibility detection does not serve this handle (nullptr: it does)
+static const char *infeas_unsupported(pdplqr_handle h) {
+    if (h->md) return "infeasibility detection: num_devices handles are not supported (E lives on the slices)";
+    if (h->cfg.solver == PDPLQR_SOLVER_KKT)
+        return "infeasibility detection: the KKT solver softens the dynamics by rho_dyn; SERIAL and PARALLEL only";
+    if (!infeas_shape_supported(h->sh)) return "infeasibility detection: nx + nu <= 64 only";
+    return nullptr;
+}
+
+static void infeas_model_args(pdplqr_handle h, InfeasArgs &q) {
+    q.sh = h->sh;
+    q.E = h->E;
+    q.c = h->c;
+    q.H = h->H;
+    q.hv = h->h;
+    q.D = h->D;
+    q.d_off = h->d_off;
+    q.y_off = h->y_off;
+    q.uni = uniform_rows(h);
+    q.max_nc = h->max_nc;
+    q.yp = q.wp = nullptr;
+    q.verdict = nullptr;
+    q.done = q.status = q.active = nullptr;
+    q.rscale = nullptr;
+}
+
+static int infeas_alloc(pdplqr_handle h) {
+    AdmmState *s = h->admm;
+    if (s->yp) return PDPLQR_OK;
+    const Shape &sh = h->sh;
+    const long long B = sh.batch;
+    int rc;
+    if ((rc = aalloc(h, &s->wp, B * sh.perh)) || (rc = aalloc(h, &s->meas, B * 8)) ||
+        (rc = aalloc(h, &s->istat, B)) || (rc = aalloc(h, &s->yp, B * sh.ny)))
+        return rc;
+    return PDPLQR_OK;
+}
+
+// a device buffer of `count` T for one call (mem = HOST: filled from `src` when given)
+template <typename T>
+struct CallBuf {
+    T *p = nullptr;
+    bool own = false;
+    ~CallBuf() {
+        if (own && p) (void)hipFree(p);
+    }
+    int in(const T *src, size_t count, int mem, hipStream_t S) {
+        if (mem == PDPLQR_MEM_DEVICE) {
+            p = const_cast<T *>(src);
+            return PDPLQR_OK;
+        }
+        if (hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
+            p = nullptr;
+            set_error("hipMalloc failed");
+            return PDPLQR_ERR_ALLOC;
+        }
+        own = true;
+        if (src) PDPLQR_HIP_TRY(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, S));
+        return PDPLQR_OK;
+    }
+};
 
 }  // namespace pdplqr
 
@@ -680,6 +759,32 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
     PDPLQR_HIP_TRY(hipMemsetAsync(s->iters, 0, B * sizeof(int32_t), S));
     PDPLQR_HIP_TRY(hipMemsetAsync(s->prim, 0, B * sizeof(double), S));
     PDPLQR_HIP_TRY(hipMemsetAsync(s->dual, 0, B * sizeof(double), S));
+    // infeasibility detection (off: nothing below launches or copies anything new)
+    const bool detect = h->infeas_on != 0;
+    const bool det_p = detect && Y > 0 && h->eps_prim_inf > 0.0, det_d = detect && Y > 0 && h->eps_dual_inf > 0.0;
+    InfeasArgs q{};
+    if (detect) {
+        if ((rc = infeas_alloc(h))) return rc;
+        PDPLQR_HIP_TRY(hipMemsetAsync(s->istat, 0, B * sizeof(int32_t), S));
+        PDPLQR_HIP_TRY(hipMemsetAsync(s->meas, 0, B * 8 * sizeof(double), S));
+        infeas_model_args(h, q);
+        q.x0 = s->x0;
+        q.lb = s->lb;
+        q.ub = s->ub;
+        q.y = s->y;
+        q.yp = s->yp;
+        q.w = s->w;
+        q.wp = s->wp;
+        q.eps_p = h->eps_prim_inf;
+        q.eps_d = h->eps_dual_inf;
+        q.meas = s->meas;
+        q.done = s->done;
+        q.status = s->istat;
+        q.active = s->active;
+        q.rscale = s->rscale;
+    }
+    s->solved_once = true;
+    s->detect_last = detect;
 
     const bool kkt = h->cfg.solver == PDPLQR_SOLVER_KKT;
     AdmmArgs a;
@@ -795,6 +900,9 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
             break;
         }
         if (check) PDPLQR_HIP_TRY(hipMemsetAsync(s->active, 0, 2 * sizeof(int32_t), S));
+        // a test iteration with detection on: keep (y^k, w^k) of the problems still iterating
+        if (check && (det_p || det_d) && (rc = launch_infeas_snapshot(sh, s->done, s->y, s->w, s->yp, s->wp, S)))
+            return rc;
         if (fuse && can_fuse) {
             // the update of this iteration and the backward_without_factorization
             // of the next in one streamed pass (kernels_nofact.hip)
@@ -805,6 +913,10 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
         }
         if (!fused && (rc = launch_admm_update(a, admm_lps(sh), fuse, check, ugrid, ublk, S))) return rc;
         if (check) {
+            // the certificates on the problems the termination test left iterating
+            // (solved takes precedence); a certified one leaves `active`
+            if (det_p && (rc = launch_infeas_primal(q, S))) return rc;
+            if (det_d && (rc = launch_infeas_dual(q, S))) return rc;
             PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, S));
             PDPLQR_HIP_TRY(hipStreamSynchronize(S));
             if (s->active_h[0] == 0) break;
@@ -852,6 +964,136 @@ int pdplqr_admm_info(pdplqr_handle h, int32_t *iters, int32_t *converged, double
     if (rho && h->sh.ny > 0)
         PDPLQR_HIP_TRY(hipMemcpy(rho, s->rho, B * h->sh.ny * sizeof(double), hipMemcpyDeviceToHost));
     return h->admm_iters;
+}
+
+int pdplqr_admm_set_infeasibility_detection(pdplqr_handle h, int enable, double eps_prim_inf, double eps_dual_inf) {
+    if (!h) return PDPLQR_ERR_INVALID;
+    if (!enable) {
+        h->infeas_on = 0;
+        return PDPLQR_OK;
+    }
+    if (!(eps_prim_inf >= 0.0) || !(eps_dual_inf >= 0.0)) {  // (NaN fails both comparisons)
+        set_error("set_infeasibility_detection: eps_prim_inf, eps_dual_inf must be >= 0 (0 switches that test off)");
+        return PDPLQR_ERR_INVALID;
+    }
+    if (const char *why = infeas_unsupported(h)) {
+        set_error(why);
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
+    h->infeas_on = 1;
+    h->eps_prim_inf = eps_prim_inf;
+    h->eps_dual_inf = eps_dual_inf;
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_status(pdplqr_handle h, int32_t *status) {
+    if (!h || !status) return PDPLQR_ERR_INVALID;
+    if (!h->admm || !h->admm->solved_once) {
+        set_error("admm_status before admm_solve");
+        return PDPLQR_ERR_STATE;
+    }
+    PDPLQR_HIP_TRY(hipSetDevice(h->md ? md_primary_device(h) : h->cfg.device));
+    PDPLQR_HIP_TRY(hipStreamSynchronize(h->md ? reinterpret_cast<hipStream_t>(md_stream(h)) : h->stream));
+    AdmmState *s = h->admm;
+    const size_t B = (size_t)h->sh.batch;
+    PDPLQR_HIP_TRY(hipMemcpy(status, s->conv, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (s->detect_last) {
+        std::vector<int32_t> st(B);
+        PDPLQR_HIP_TRY(hipMemcpy(st.data(), s->istat, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < B; ++b)
+            if (st[b]) status[b] = st[b];  // (a certified problem has converged = 0)
+    }
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_certificate(pdplqr_handle h, double *dy, double *dw, int mem) {
+    if (!h) return PDPLQR_ERR_INVALID;
+    if (!h->admm || !h->admm->solved_once || !h->admm->detect_last) {
+        set_error("admm_certificate: the last admm_solve did not run with infeasibility detection on");
+        return PDPLQR_ERR_STATE;
+    }
+    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    AdmmState *s = h->admm;
+    hipStream_t S = h->stream;
+    const Shape &sh = h->sh;
+    const long long B = sh.batch, W = B * sh.perh, Y = B * sh.ny;
+    int rc;
+    CallBuf<double> by, bw;
+    if (dy && Y > 0) {
+        if ((rc = by.in(nullptr, (size_t)Y, mem, S))) return rc;
+        if (mem == PDPLQR_MEM_DEVICE) by.p = dy;
+        if ((rc = launch_infeas_delta(Y, sh.ny, s->istat, s->y, s->yp, by.p, S))) return rc;
+        if (mem != PDPLQR_MEM_DEVICE)
+            PDPLQR_HIP_TRY(hipMemcpyAsync(dy, by.p, Y * sizeof(double), hipMemcpyDeviceToHost, S));
+    }
+    if (dw) {
+        if ((rc = bw.in(nullptr, (size_t)W, mem, S))) return rc;
+        if (mem == PDPLQR_MEM_DEVICE) bw.p = dw;
+        if ((rc = launch_infeas_delta(W, sh.perh, s->istat, s->w, s->wp, bw.p, S))) return rc;
+        if (mem != PDPLQR_MEM_DEVICE)
+            PDPLQR_HIP_TRY(hipMemcpyAsync(dw, bw.p, W * sizeof(double), hipMemcpyDeviceToHost, S));
+    }
+    if (mem != PDPLQR_MEM_DEVICE) PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_check_certificates(pdplqr_handle h, const double *x0, const double *lb, const double *ub,
+                                   const double *dy, const double *dw, double eps_prim_inf,
+                                   double eps_dual_inf, double *measures, int32_t *verdict, int mem) {
+    if (!h || !measures || !verdict) return PDPLQR_ERR_INVALID;
+    if (const char *why = infeas_unsupported(h)) {
+        set_error(why);
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
+    if (!h->model_set) {
+        set_error("admm_check_certificates before set_model");
+        return PDPLQR_ERR_STATE;
+    }
+    const Shape &sh = h->sh;
+    if ((dy && !x0) || (sh.ny > 0 && (!lb || !ub))) {
+        set_error("admm_check_certificates: null x0 / lb / ub");
+        return PDPLQR_ERR_INVALID;
+    }
+    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t S = h->stream;
+    const size_t B = (size_t)sh.batch, W = B * sh.perh, Y = B * sh.ny;
+    int rc;
+    CallBuf<double> bx, bl, bu, by, bw, bm;
+    CallBuf<int32_t> bv;
+    if ((rc = bm.in(nullptr, B * 8, mem, S)) || (rc = bv.in(nullptr, B, mem, S))) return rc;
+    if (mem == PDPLQR_MEM_DEVICE) {
+        bm.p = measures;
+        bv.p = verdict;
+    }
+    PDPLQR_HIP_TRY(hipMemsetAsync(bm.p, 0, B * 8 * sizeof(double), S));
+    PDPLQR_HIP_TRY(hipMemsetAsync(bv.p, 0, B * sizeof(int32_t), S));
+    if (Y > 0 && ((rc = bl.in(lb, Y, mem, S)) || (rc = bu.in(ub, Y, mem, S)))) return rc;
+    InfeasArgs q;
+    infeas_model_args(h, q);
+    q.lb = bl.p;
+    q.ub = bu.p;
+    q.eps_p = eps_prim_inf;
+    q.eps_d = eps_dual_inf;
+    q.meas = bm.p;
+    q.verdict = bv.p;
+    q.x0 = q.y = q.w = nullptr;
+    if (dy && Y > 0) {
+        if ((rc = bx.in(x0, B * sh.n, mem, S)) || (rc = by.in(dy, Y, mem, S))) return rc;
+        q.x0 = bx.p;
+        q.y = by.p;
+        if ((rc = launch_infeas_primal(q, S))) return rc;
+    }
+    if (dw) {
+        if ((rc = bw.in(dw, W, mem, S))) return rc;
+        q.w = bw.p;
+        if ((rc = launch_infeas_dual(q, S))) return rc;
+    }
+    if (mem != PDPLQR_MEM_DEVICE) {
+        PDPLQR_HIP_TRY(hipMemcpyAsync(measures, bm.p, B * 8 * sizeof(double), hipMemcpyDeviceToHost, S));
+        PDPLQR_HIP_TRY(hipMemcpyAsync(verdict, bv.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, S));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    }
+    return PDPLQR_OK;
 }
 
 }  // extern "C"

@@ -51,6 +51,30 @@ __device__ __forceinline__ void admm_decide(const AdmmArgs &a, int b, double rp,
     a.rscale[b] = f;
 }
 
+// Infeasibility certificates (kernels_infeas.hip).  The
+// vectors tested are y - yp and w - wp (the loop: differences of consecutive
+// iterates) or y and w themselves (yp, wp null: the stand-alone evaluator).
+struct InfeasArgs {
+    Shape sh;
+    const double *E, *c, *H, *hv, *D, *x0, *lb, *ub;
+    const double *y, *yp, *w, *wp;
+    const int32_t *d_off, *y_off;
+    int uni, max_nc;
+    double eps_p, eps_d;
+    double *meas;      // [b][8]: |dy|, max|g|, support - beta, infinite-bound flag; |dw|, max|H dw|, h^T dw, violation
+    int32_t *verdict;  // [b] bit 0 primal, bit 1 dual (nullable)
+    // the loop (done non-null): problems with done[b] != 0 are skipped, a certified one is frozen
+    int32_t *done, *status, *active;
+    double *rscale;
+};
+bool infeas_shape_supported(const Shape &sh);  // n + m <= 64
+int launch_infeas_primal(const InfeasArgs &a, hipStream_t st);
+int launch_infeas_dual(const InfeasArgs &a, hipStream_t st);
+int launch_infeas_snapshot(const Shape &sh, const int32_t *done, const double *y, const double *w, double *yp,
+                           double *wp, hipStream_t st);
+int launch_infeas_delta(long long total, long long per, const int32_t *status, const double *cur, const double *prev,
+                        double *out, hipStream_t st);
+
 // Fused ADMM update + backward_without_factorization (kernels_nofact.hip):
 // PDPLQR_ERR_UNSUPPORTED when the shape / constraint layout is not covered.
 int launch_nofact_admm(const RiccatiArgs &r, const AdmmArgs &a, bool check, hipStream_t st);

@@ -175,6 +175,9 @@ struct pdplqr_handle_s {
     pdplqr::AdjointState *adj = nullptr;   // pdplqr_adjoint scratch (adjoint.hip), allocated on first use
     int admm_iters = 0;                    // iterations of the last admm_solve
     int admm_rho_updates = 0;              // adaptive-rho refactorizations of the last admm_solve
+    // pdplqr_admm_set_infeasibility_detection (admm.hip, kernels_infeas.hip)
+    int infeas_on = 0;
+    double eps_prim_inf = 1e-4, eps_dual_inf = 1e-4;
     int shard_last = 1;  // last shard_backward's is_last_shard
     pdplqr::MultiDev *md = nullptr;  // num_devices > 1 (multidev.hip): the slices' handles
     // replayable launch sequences of backward / backward_without_factorization /

@@ -20,6 +20,11 @@ PDPLQR_SOLVER_PARALLEL = 1
 PDPLQR_SOLVER_KKT = 2
 PDPLQR_CONDENSED_LU = 0
 PDPLQR_CONDENSED_CHOLESKY = 1
+# pdplqr_admm_status
+PDPLQR_ADMM_UNSOLVED = 0
+PDPLQR_ADMM_SOLVED = 1
+PDPLQR_ADMM_PRIMAL_INFEASIBLE = 2
+PDPLQR_ADMM_DUAL_INFEASIBLE = 3
 
 ERRORS = {-1: "INVALID", -2: "HIP", -3: "ALLOC", -4: "STATE", -5: "UNSUPPORTED", -6: "NUMERIC"}
 
@@ -34,6 +39,8 @@ EXPORTS = [
     "pdplqr_device_count",
     "pdplqr_admm_settings_init", "pdplqr_admm_solve", "pdplqr_admm_info", "pdplqr_multidev_plan",
     "pdplqr_adjoint", "pdplqr_adjoint_rows",
+    "pdplqr_admm_set_infeasibility_detection", "pdplqr_admm_status", "pdplqr_admm_certificate",
+    "pdplqr_admm_check_certificates",
 ]
 
 
@@ -112,6 +119,11 @@ def lib() -> C.CDLL:
     L.pdplqr_admm_settings_init.restype = None
     L.pdplqr_admm_solve.argtypes = [vp, C.POINTER(AdmmSettings), dp, dp, dp, dp, dp, dp, dp, C.c_int]
     L.pdplqr_admm_info.argtypes = [vp, ip, ip, dp, dp, dp]
+    if hasattr(L, "pdplqr_admm_status"):  # (absent from older A/B variants)
+        L.pdplqr_admm_set_infeasibility_detection.argtypes = [vp, C.c_int, C.c_double, C.c_double]
+        L.pdplqr_admm_status.argtypes = [vp, ip]
+        L.pdplqr_admm_certificate.argtypes = [vp, dp, dp, C.c_int]
+        L.pdplqr_admm_check_certificates.argtypes = [vp, dp, dp, dp, dp, dp, C.c_double, C.c_double, dp, vp, C.c_int]
     if hasattr(L, "pdplqr_adjoint"):  # (absent from older A/B variants)
         L.pdplqr_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_adjoint_rows"):  # (absent from older A/B variants)

@@ -113,6 +113,15 @@ class _BoxLQRSolve(torch.autograd.Function):
         layer._gen += 1  # the handle now holds THIS call's factorization
         ctx.layer, ctx.gen = layer, layer._gen
         ctx.converged = bool(layer.admm_info["converged"].all())
+        ctx.infeasible = None  # (index, kind) of the first problem certified infeasible / unbounded
+        if layer.detect_infeasible:
+            bad = (layer.admm_info["status"] >= _lib.PDPLQR_ADMM_PRIMAL_INFEASIBLE).nonzero()[0]
+            if bad.size:
+                b = int(bad[0])
+                kind = ("primal infeasible (no point satisfies the dynamics and lb <= D w <= ub)"
+                        if layer.admm_info["status"][b] == _lib.PDPLQR_ADMM_PRIMAL_INFEASIBLE
+                        else "dual infeasible (the cost is unbounded below)")
+                ctx.infeasible = (b, kind)
         ctx.shapes = [t.shape for t in (E, c, H, h, x0, D, lb, ub)]
         ctx.save_for_backward(wt, ys, zs, ins[6], ins[7])
         return ws
@@ -126,6 +135,10 @@ class _BoxLQRSolve(torch.autograd.Function):
                 "BoxLQRLayer: backward through a solution whose factorization is gone: the layer was called again "
                 f"(call {layer._gen}) after the call being differentiated (call {ctx.gen}), and its handle keeps "
                 "one factorization.  Call backward before the next forward, or use one BoxLQRLayer per live graph.")
+        if ctx.infeasible is not None:  # (allow_unconverged does not override: there is no optimum)
+            raise RuntimeError(
+                f"BoxLQRLayer: problem {ctx.infeasible[0]} of the batch is {ctx.infeasible[1]} (layer.admm_info"
+                '["status"]); there is no optimum to differentiate.')
         if not ctx.converged and not layer.allow_unconverged:
             raise RuntimeError(
                 "BoxLQRLayer: the ADMM solve being differentiated did not converge for every problem of the batch "
@@ -196,17 +209,25 @@ class BoxLQRLayer:
     ``RuntimeError`` if a problem did not converge (unless
     ``allow_unconverged``), or if the layer was called again in between (the
     handle keeps ONE factorization).  ``admm_info`` holds the last solve's
-    outcome, ``adjoint_iterations`` the last backward's count."""
+    outcome, ``adjoint_iterations`` the last backward's count.
+
+    ``detect_infeasible``: run OSQP's infeasibility certificates in the solve
+    (``admm_info["status"]``: 2 = no feasible point, 3 = cost unbounded below);
+    ``backward`` then raises ``RuntimeError`` naming the first such problem and
+    its kind, before the "did not converge" error and whatever
+    ``allow_unconverged`` says."""
 
     def __init__(self, n: int, m: int, N: int, batch: int, ncs, rho, sigma: float = 1e-6, alpha: float = 1.6,
                  eps: float = 1e-6, max_iter: int = 4000, adj_tol: float = 1e-8, adj_max_iter: int = 4000,
-                 check_every: int = 25, allow_unconverged: bool = False, device: int = 0):
+                 check_every: int = 25, allow_unconverged: bool = False, device: int = 0,
+                 detect_infeasible: bool = False, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
         from .solvers import admm_settings
 
         self.n, self.m, self.N, self.batch = int(n), int(m), int(N), int(batch)
         self.sigma, self.alpha = float(sigma), float(alpha)
         self.adj_tol, self.adj_max_iter, self.check_every = float(adj_tol), int(adj_max_iter), int(check_every)
         self.allow_unconverged = bool(allow_unconverged)
+        self.detect_infeasible = bool(detect_infeasible)
         s = n + m
         ncs = [int(x) for x in ncs]
         if len(ncs) != N + 1:
@@ -223,6 +244,8 @@ class BoxLQRLayer:
         self._rho = (rho.expand(batch, self.ny) if rho.numel() == 1 else rho.reshape(batch, self.ny)).contiguous()
         self._irho = (1.0 / self._rho).contiguous()
         self._settings = admm_settings(sigma, alpha, max_iter, check_every, eps, 0.0, False)
+        if self.detect_infeasible:
+            self._hd.set_infeasibility_detection(True, eps_prim_inf, eps_dual_inf)
         self._gen = 0
         self.admm_info = None
         self.adjoint_iterations = 0

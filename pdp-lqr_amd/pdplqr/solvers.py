@@ -276,7 +276,60 @@ class _Handle:
                                          C.c_void_p(rp.ctypes.data), C.c_void_p(rd.ctypes.data),
                                          C.c_void_p(rho.ctypes.data)))
         return {"iterations": int(n), "iters": it, "converged": cv.astype(bool), "prim_res": rp, "dual_res": rd,
-                "rho": rho[:, :self.ny]}
+                "rho": rho[:, :self.ny], "status": self.admm_status()}
+
+    def set_infeasibility_detection(self, enable: bool, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
+        """Switch OSQP's infeasibility certificates of ``admm_solve`` on or off
+        (include/pdplqr.h: pdplqr_admm_set_infeasibility_detection)."""
+        check(lib().pdplqr_admm_set_infeasibility_detection(self.h, int(bool(enable)), float(eps_prim_inf),
+                                                            float(eps_dual_inf)))
+
+    def admm_status(self) -> np.ndarray:
+        """PDPLQR_ADMM_* per problem after the last admm_solve: 0 unsolved, 1 solved,
+        2 primal infeasible, 3 dual infeasible (cost unbounded below)."""
+        out = np.zeros(self.batch, dtype=np.int32)
+        check(lib().pdplqr_admm_status(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def admm_certificate(self, dy=None, dw=None):
+        """The dy / dw of the deciding test for the problems with status 2 / 3
+        (zeros for the rest), into the given buffers; with none given, returns
+        new host arrays ``(dy, dw)``."""
+        if dy is None and dw is None:
+            dy = np.zeros((self.batch, self.ny))
+            dw = np.zeros((self.batch, self.N * (self.nx + self.nu) + self.nx))
+        ps = [_ptr(dy, "dy"), _ptr(dw, "dw")]
+        cur = self._enter(dy, dw)
+        check(lib().pdplqr_admm_certificate(self.h, ps[0][0], ps[1][0], _mem_of(*ps)))
+        self._leave(cur)
+        return dy, dw
+
+    def check_certificates(self, x0, lb, ub, dy=None, dw=None, eps_prim_inf: float = 1e-4,
+                           eps_dual_inf: float = 1e-4):
+        """The two certificate tests on given vectors (pdplqr_admm_check_certificates;
+        needs only set_model).  Host (numpy) or device (torch) inputs; returns
+        ``(measures [batch][8], verdict [batch])`` in the same memory: verdict bit 0
+        = primal infeasible, bit 1 = dual infeasible.  ``dy`` / ``dw`` None skips
+        that half."""
+        objs = [x0, lb, ub, dy, dw]
+        ps = [_ptr(o, nm) for o, nm in zip(objs, ("x0", "lb", "ub", "dy", "dw"))]
+        mem = _mem_of(*ps)
+        if mem == _lib.PDPLQR_MEM_DEVICE:
+            import torch
+
+            dev = next(o for o in objs if o is not None).device
+            meas = torch.zeros(self.batch, 8, dtype=torch.float64, device=dev)
+            verdict = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+            pm, pv = C.c_void_p(meas.data_ptr()), C.c_void_p(verdict.data_ptr())
+        else:
+            meas = np.zeros((self.batch, 8))
+            verdict = np.zeros(self.batch, dtype=np.int32)
+            pm, pv = C.c_void_p(meas.ctypes.data), C.c_void_p(verdict.ctypes.data)
+        cur = self._enter(*objs, meas)
+        check(lib().pdplqr_admm_check_certificates(self.h, *[p[0] for p in ps], float(eps_prim_inf),
+                                                   float(eps_dual_inf), pm, pv, mem))
+        self._leave(cur)
+        return meas, verdict
 
     def segments(self, ns: int):
         a = np.zeros(ns, dtype=np.int32)
@@ -351,7 +404,8 @@ class _ModelSolver:
 
     def admm_solve(self, x0, ws: List[np.ndarray], ys, zs, rho_vecs, sigma: float = 1e-6, alpha: float = 1.6,
                    max_iter: int = 4000, check_every: int = 25, eps_abs: float = 1e-3, eps_rel: float = 1e-3,
-                   adaptive_rho: bool = True, adaptive_rho_tolerance: float = 5.0):
+                   adaptive_rho: bool = True, adaptive_rho_tolerance: float = 5.0,
+                   detect_infeasibility: bool = False, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
         """ADMM outer loop over this solver (new: absent in the reference,
         README.md:8) for the bounds ``e_lb <= D_con w <= e_ub`` stored in the
         model's nodes (lqr_model.hpp:21-24).  ``ws, ys, zs`` are the warm start
@@ -367,6 +421,10 @@ class _ModelSolver:
         y, z, r = self._y(ys), self._y(zs), self._y(rho_vecs)
         st = admm_settings(sigma, alpha, max_iter, check_every, eps_abs, eps_rel, adaptive_rho,
                            adaptive_rho_tolerance)
+        if detect_infeasibility:  # (off: the handle's default; unsupported kinds raise here)
+            self._hd.set_infeasibility_detection(True, eps_prim_inf, eps_dual_inf)
+        else:
+            self._hd.set_infeasibility_detection(False)
         self._hd.admm_solve(np.ascontiguousarray(x0, dtype=np.float64), lb, ub, r, w, y, z, st)
         s = m.n + m.m
         for k in range(m.N):
@@ -381,7 +439,7 @@ class _ModelSolver:
         info = self._hd.admm_info()
         return {"iterations": info["iterations"], "iters": int(info["iters"][0]),
                 "converged": bool(info["converged"][0]), "prim_res": float(info["prim_res"][0]),
-                "dual_res": float(info["dual_res"][0])}
+                "dual_res": float(info["dual_res"][0]), "status": int(info["status"][0])}
 
 
 class LQRSolver(_ModelSolver):
@@ -497,14 +555,26 @@ class BatchedLQRSolver:
 
     def admm_solve(self, x0, lb, ub, rho, ws, ys=None, zs=None, sigma: float = 1e-6, alpha: float = 1.6,
                    max_iter: int = 4000, check_every: int = 25, eps_abs: float = 1e-3, eps_rel: float = 1e-3,
-                   adaptive_rho: bool = True, adaptive_rho_tolerance: float = 5.0):
+                   adaptive_rho: bool = True, adaptive_rho_tolerance: float = 5.0,
+                   detect_infeasibility: bool = False, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
         """ADMM outer loop for the box constraints lb <= D w <= ub on the device
         (include/pdplqr.h: pdplqr_admm_solve).  ws/ys/zs hold the warm start and
-        are overwritten with the solution; returns admm_info()."""
+        are overwritten with the solution; returns admm_info().
+        ``detect_infeasibility``: recognise problems with no feasible point or a
+        cost unbounded below at the termination tests (``admm_info()["status"]``
+        2 / 3; ``admm_certificate()`` has the certificates)."""
         st = admm_settings(sigma, alpha, max_iter, check_every, eps_abs, eps_rel, adaptive_rho,
                            adaptive_rho_tolerance)
+        self._hd.set_infeasibility_detection(detect_infeasibility, eps_prim_inf, eps_dual_inf)
         self._hd.admm_solve(x0, lb, ub, rho, ws, ys, zs, st)
         return self._hd.admm_info()
+
+    def admm_certificate(self, dy=None, dw=None):
+        return self._hd.admm_certificate(dy, dw)
+
+    def check_certificates(self, x0, lb, ub, dy=None, dw=None, eps_prim_inf: float = 1e-4,
+                           eps_dual_inf: float = 1e-4):
+        return self._hd.check_certificates(x0, lb, ub, dy, dw, eps_prim_inf, eps_dual_inf)
 
     def admm_info(self):
         return self._hd.admm_info()
