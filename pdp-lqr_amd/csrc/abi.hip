@@ -33,24 +33,25 @@ static int invalid(const std::string &msg) {
     return PDPLQR_ERR_INVALID;
 }
 
-template <typename X>
-static int dalloc(pdplqr_handle h, X **p, size_t count) {
+int dev_alloc_bytes(pdplqr_handle h, void **p, size_t bytes) {
     *p = nullptr;
-    if (count == 0) count = 1;
     void *q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(X));
+    hipError_t e = hipMalloc(&q, bytes);
     if (e != hipSuccess) {
-        set_error(std::string("hipMalloc(") + std::to_string(count * sizeof(X)) + " B): " + hipGetErrorString(e));
+        set_error(std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(e));
         return PDPLQR_ERR_ALLOC;
     }
     h->allocs.push_back(q);
-    *p = reinterpret_cast<X *>(q);
+    *p = q;
     return PDPLQR_OK;
 }
 
-// Copies `count` doubles from host or device memory into device buffer `dst`
-// (or returns the device pointer itself when no copy is needed).
-static int stage_in(pdplqr_handle h, const double *src, double *dst, long long count, int mem, const double **out) {
+int bind_device(pdplqr_handle h) {
+    PDPLQR_HIP_TRY(hipSetDevice(h->md ? md_primary_device(h) : h->cfg.device));
+    return PDPLQR_OK;
+}
+
+int stage_in(pdplqr_handle h, const double *src, double *dst, long long count, int mem, const double **out) {
     if (count <= 0) {
         *out = dst;
         return PDPLQR_OK;
@@ -64,6 +65,31 @@ static int stage_in(pdplqr_handle h, const double *src, double *dst, long long c
     h->host_staged = true;
     *out = dst;
     return PDPLQR_OK;
+}
+
+int stage_out(pdplqr_handle h, double *dst, const double *src, long long count, int mem) {
+    if (mem == PDPLQR_MEM_DEVICE) return PDPLQR_OK;
+    PDPLQR_HIP_TRY(hipMemcpyAsync(dst, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
+    h->host_staged = false;
+    return PDPLQR_OK;
+}
+
+RiccatiArgs riccati_args(pdplqr_handle h) {
+    RiccatiArgs a;
+    a.sh = h->sh;
+    a.E = h->E;
+    a.c = h->c;
+    a.Hw = h->Hw;
+    a.hw = h->hw;
+    a.KD = h->KD;
+    a.Lc = h->Lc;
+    a.lpc = h->lpc;
+    a.status = h->status;
+    a.tab_s = h->tab_s;
+    a.tab_n = h->tab_n;
+    a.xl_ws = h->xl_ws;
+    return a;
 }
 
 }  // namespace pdplqr
@@ -187,10 +213,10 @@ int pdplqr_create(const pdplqr_config *cfg, pdplqr_handle *out) {
     h->stream = h->own_stream;
     sh.x1 = one_wave_per_simd(C.device, sh.batch);
     const long long B = sh.batch;
-#define ALLOC(ptr, cnt)                                  \
-    do {                                                 \
-        if ((rc = dalloc(h, &(ptr), (size_t)(cnt))) != 0) \
-            goto fail;                                   \
+#define ALLOC(ptr, cnt)                                      \
+    do {                                                     \
+        if ((rc = dev_alloc(h, &(ptr), (size_t)(cnt))) != 0) \
+            goto fail;                                       \
     } while (0)
     ALLOC(h->E, B * sh.perE);
     ALLOC(h->c, B * sh.perc);
@@ -285,7 +311,7 @@ int pdplqr_set_stream(pdplqr_handle h, void *stream) {
         // precedes everything queued on the new one: without this a model
         // uploaded before the switch can still be in flight when the first
         // kernel on the new stream reads it
-        PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+        if (int brc = bind_device(h)) return brc;
         hipEvent_t ev;
         PDPLQR_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         hipError_t e = hipEventRecord(ev, h->stream);
@@ -305,7 +331,7 @@ void *pdplqr_get_stream(pdplqr_handle h) {
 int pdplqr_synchronize(pdplqr_handle h) {
     if (!h) return invalid("null handle");
     if (h->md) return md_synchronize(h);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
     return PDPLQR_OK;
 }
@@ -320,7 +346,7 @@ int pdplqr_set_model_arrays(pdplqr_handle h, int mask, const double *E, const do
         return invalid("set_model: null E/c/H/h");
     if ((mask & PDPLQR_MODEL_D) && h->sh.ndD > 0 && !D) return invalid("set_model: constraints declared but D is null");
     if (h->md) return md_set_model(h, mask, E, c, H, hv, D, mem);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     const Shape &sh = h->sh;
     const long long B = sh.batch;
     const hipMemcpyKind kind = mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -381,7 +407,7 @@ int pdplqr_update_problem_data(pdplqr_handle h, const double *ws, const double *
         return PDPLQR_ERR_STATE;
     }
     if (h->md) return md_update(h, ws, ys, zs, inv_rho, sigma, mem);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     const Shape &sh = h->sh;
     const long long B = sh.batch;
     const double *dws, *dy = h->st_y, *dz = h->st_z, *dir = h->st_ir;
@@ -411,7 +437,7 @@ static int backward_common(pdplqr_handle h, const double *rho, int mem, bool fac
         return PDPLQR_ERR_STATE;
     }
     if (h->md) return md_backward(h, rho, mem, fact);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     h->host_staged = false;
     const Shape &sh = h->sh;
     const double *drho = h->st_rho;
@@ -447,7 +473,7 @@ int pdplqr_forward(pdplqr_handle h, const double *x0, double *ws, int mem) {
     }
     if (!x0 || !ws) return invalid("forward: null x0/ws");
     if (h->md) return md_forward(h, x0, ws, mem);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     const Shape &sh = h->sh;
     const double *dx0;
     int rc;
@@ -456,18 +482,13 @@ int pdplqr_forward(pdplqr_handle h, const double *x0, double *ws, int mem) {
     rc = solver_forward(h, dx0, dws);
     if (rc) return rc;
     h->host_staged = false;
-    if (mem != PDPLQR_MEM_DEVICE) {
-        PDPLQR_HIP_TRY(hipMemcpyAsync(ws, dws, (size_t)sh.batch * sh.perh * sizeof(double), hipMemcpyDeviceToHost,
-                                      h->stream));
-        PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return PDPLQR_OK;
+    return stage_out(h, ws, dws, (long long)sh.batch * sh.perh, mem);
 }
 
 int pdplqr_clear_workspace(pdplqr_handle h) {
     if (!h) return invalid("null handle");
     if (h->md) return md_clear(h);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     const Shape &sh = h->sh;
     const long long B = sh.batch;
     PDPLQR_HIP_TRY(hipMemsetAsync(h->Hw, 0, B * sh.perHw * sizeof(double), h->stream));
@@ -493,7 +514,7 @@ int pdplqr_get_value_function(pdplqr_handle h, int32_t b, int32_t k, double *P, 
         set_error("get_value_function before backward");
         return PDPLQR_ERR_STATE;
     }
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     const int dim = k < sh.N ? sh.s : sh.n, off = dim - sh.n;
     const int pk = k < sh.N ? sh.ps : sh.pn;
     std::vector<double> Lp(pk), lp(dim);
@@ -522,7 +543,7 @@ int pdplqr_get_value_function(pdplqr_handle h, int32_t b, int32_t k, double *P, 
 int pdplqr_get_status(pdplqr_handle h, int32_t *flags) {
     if (!h || !flags) return invalid("null argument");
     if (h->md) return md_status(h, flags);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
     return solver_status(h, flags);
 }

@@ -35,33 +35,55 @@ void adjoint_release(pdplqr_handle h) {
     h->adj = nullptr;
 }
 
-static int jalloc(pdplqr_handle h, double **p, long long count) {
-    *p = nullptr;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, (size_t)(count > 0 ? count : 1) * sizeof(double));
-    if (e != hipSuccess) {
-        set_error(std::string("adjoint: hipMalloc: ") + hipGetErrorString(e));
-        return PDPLQR_ERR_ALLOC;
-    }
-    h->allocs.push_back(q);
-    *p = reinterpret_cast<double *>(q);
-    return PDPLQR_OK;
-}
-
 static int adjoint_alloc(pdplqr_handle h) {
     if (h->adj) return PDPLQR_OK;
     const Shape &sh = h->sh;
     const long long B = sh.batch;
     AdjointState s;
     int rc;
-    if ((rc = jalloc(h, &s.zc, B * sh.perc)) || (rc = jalloc(h, &s.zx0, B * sh.n)) ||
-        (rc = jalloc(h, &s.rhs, B * sh.perh)) || (rc = jalloc(h, &s.v, B * sh.perh)) ||
-        (rc = jalloc(h, &s.lpa, B * sh.perh)) || (rc = jalloc(h, &s.lus, B * sh.N * sh.m)))
+    if ((rc = dev_alloc(h, &s.zc, B * sh.perc)) || (rc = dev_alloc(h, &s.zx0, B * sh.n)) ||
+        (rc = dev_alloc(h, &s.rhs, B * sh.perh)) || (rc = dev_alloc(h, &s.v, B * sh.perh)) ||
+        (rc = dev_alloc(h, &s.lpa, B * sh.perh)) || (rc = dev_alloc(h, &s.lus, B * sh.N * sh.m)))
         return rc;
     PDPLQR_HIP_TRY(hipMemsetAsync(s.zc, 0, (size_t)(B * sh.perc) * sizeof(double), h->stream));
     PDPLQR_HIP_TRY(hipMemsetAsync(s.zx0, 0, (size_t)(B * sh.n) * sizeof(double), h->stream));
     h->adj = new AdjointState(s);
     return PDPLQR_OK;
+}
+
+// the rows kernel's pointers on a block adjoint_rows_plan laid out: the
+// handle's rows and the adjoint solution in the scratch, the call's vectors
+static void adjoint_rows_args(pdplqr_handle h, AdjointRowsArgs &ra, const double *ws, const double *rho,
+                              const double *gvs, double *gD, double *gg, double *grho) {
+    ra.ws = ws;
+    ra.v = h->adj->v;
+    ra.D = h->D;
+    ra.rho = rho;
+    ra.g = h->gw;
+    ra.gvs = gvs;
+    ra.d_off = h->d_off;
+    ra.y_off = h->y_off;
+    ra.gD = gD;
+    ra.gg = gg;
+    ra.grho = grho;
+}
+
+// the gradient pass's arguments: the cached factor, both solves' lp and the adjoint solution
+static AdjointArgs adjoint_args(pdplqr_handle h, const double *ws, double *gE, double *gc, double *gH, double *gh,
+                                double *gx) {
+    AdjointArgs g;
+    g.sh = h->sh;
+    g.ws = ws;
+    g.v = h->adj->v;
+    g.Lc = h->Lc;
+    g.lpc = h->lpc;
+    g.lpa = h->adj->lpa;
+    g.gE = gE;
+    g.gc = gc;
+    g.gH = gH;
+    g.gh = gh;
+    g.gx = gx;
+    return g;
 }
 
 static int fail(int code, const char *msg) {
@@ -78,7 +100,7 @@ using namespace pdplqr;
 // pdplqr_adjoint, whose handles have no rows.
 static int adjoint_run(pdplqr_handle h, const char *what, const double *ws, const double *rho, const double *gws,
                        const double *gvs, double *const user[8], int mem) {
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     const Shape &sh = h->sh;
     AdjointRowsArgs ra;
     if (sh.ny > 0 && !adjoint_rows_plan(sh, h->y_off_h.data(), h->d_off_h.data(), ra))
@@ -95,19 +117,14 @@ static int adjoint_run(pdplqr_handle h, const char *what, const double *ws, cons
     // inputs: ws is read in place on the device (host: staged as forward's output is);
     // the right-hand side is formed in the scratch buffer (a copy of dl/dw, or k_adjoint_rhs
     // reading it), so the recursion's kernel choice never depends on the caller's alignment
-    const double *dws = ws, *drho = rho, *dgvs = gvs;
-    if (!dev) {
-        PDPLQR_HIP_TRY(hipMemcpyAsync(h->st_ws, ws, (size_t)(B * sh.perh) * sizeof(double), hipMemcpyHostToDevice, st));
-        dws = h->st_ws;
-        if (sh.ny > 0) {
-            if (!s->rho && (rc = jalloc(h, &s->rho, B * sh.ny))) return rc;
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->rho, rho, (size_t)(B * sh.ny) * sizeof(double), in, st));
-            drho = s->rho;
-            if (gvs) {
-                if (!s->gvs && (rc = jalloc(h, &s->gvs, B * sh.ny))) return rc;
-                PDPLQR_HIP_TRY(hipMemcpyAsync(s->gvs, gvs, (size_t)(B * sh.ny) * sizeof(double), in, st));
-                dgvs = s->gvs;
-            }
+    const double *dws, *drho = rho, *dgvs = gvs;
+    if ((rc = stage_in(h, ws, h->st_ws, B * sh.perh, mem, &dws))) return rc;
+    if (!dev && sh.ny > 0) {
+        if (!s->rho && (rc = dev_alloc(h, &s->rho, B * sh.ny))) return rc;
+        if ((rc = stage_in(h, rho, s->rho, B * sh.ny, mem, &drho))) return rc;
+        if (gvs) {
+            if (!s->gvs && (rc = dev_alloc(h, &s->gvs, B * sh.ny))) return rc;
+            if ((rc = stage_in(h, gvs, s->gvs, B * sh.ny, mem, &dgvs))) return rc;
         }
     }
     // the adjoint solve's right-hand side: dl/dw (+ D^T dl/d(D w))
@@ -125,56 +142,26 @@ static int adjoint_run(pdplqr_handle h, const char *what, const double *ws, cons
     for (int i = 0; i < 8; ++i) {
         out[i] = cnt[i] > 0 ? user[i] : nullptr;
         if (out[i] && !dev) {
-            if (!s->out[i] && (rc = jalloc(h, &s->out[i], cnt[i]))) return rc;
+            if (!s->out[i] && (rc = dev_alloc(h, &s->out[i], cnt[i]))) return rc;
             out[i] = s->out[i];
         }
     }
 
     // v: backward_without_factorization + forward of (E, H~) with h~ := g, c := 0, x0 := 0
     if ((rc = launch_adjoint_lu(sh, h->KD, s->lus, false, st))) return rc;
-    RiccatiArgs a;
-    a.sh = sh;
-    a.E = h->E;
+    RiccatiArgs a = riccati_args(h);  // (xl_ws: null on these handles, n + m <= 64)
     a.c = s->zc;
-    a.Hw = h->Hw;
     a.hw = s->rhs;
-    a.KD = h->KD;
-    a.Lc = h->Lc;
     a.lpc = s->lpa;
-    a.status = h->status;
-    a.tab_s = h->tab_s;
-    a.tab_n = h->tab_n;
     rc = launch_riccati_backward_nofact(a, st);
     if (!rc) rc = launch_riccati_forward(sh, h->E, s->zc, h->KD, s->zx0, s->v, st);
     // the record's lu' goes back whatever the launches returned
     const int rc2 = launch_adjoint_lu(sh, h->KD, s->lus, true, st);
     if (rc || rc2) return rc ? rc : rc2;
 
-    AdjointArgs g;
-    g.sh = sh;
-    g.ws = dws;
-    g.v = s->v;
-    g.Lc = h->Lc;
-    g.lpc = h->lpc;
-    g.lpa = s->lpa;
-    g.gE = out[0];
-    g.gc = out[1];
-    g.gH = out[2];
-    g.gh = out[3];
-    g.gx = out[4];
-    if ((rc = launch_adjoint_grad(g, st))) return rc;
+    if ((rc = launch_adjoint_grad(adjoint_args(h, dws, out[0], out[1], out[2], out[3], out[4]), st))) return rc;
     if (out[5] || out[6] || out[7]) {
-        ra.ws = dws;
-        ra.v = s->v;
-        ra.D = h->D;
-        ra.rho = drho;
-        ra.g = h->gw;
-        ra.gvs = dgvs;
-        ra.d_off = h->d_off;
-        ra.y_off = h->y_off;
-        ra.gD = out[5];
-        ra.gg = out[6];
-        ra.grho = out[7];
+        adjoint_rows_args(h, ra, dws, drho, dgvs, out[5], out[6], out[7]);
         if ((rc = launch_adjoint_rows(ra, h->y_off_h.data(), h->d_off_h.data(), st))) return rc;
     }
 
@@ -235,21 +222,11 @@ extern "C" int pdplqr_debug_adjoint_rows(pdplqr_handle h, const double *ws, cons
                                          double *gD, double *gg, double *grho) {
     if (!h || !ws || !rho || !h->adj || h->sh.ny == 0)
         return fail(PDPLQR_ERR_STATE, "debug_adjoint_rows before adjoint_rows");
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     AdjointRowsArgs ra;
     if (!adjoint_rows_plan(h->sh, h->y_off_h.data(), h->d_off_h.data(), ra))
         return fail(PDPLQR_ERR_UNSUPPORTED, "debug_adjoint_rows: rows exceed the LDS tile");
-    ra.ws = ws;
-    ra.v = h->adj->v;
-    ra.D = h->D;
-    ra.rho = rho;
-    ra.g = h->gw;
-    ra.gvs = gvs;
-    ra.d_off = h->d_off;
-    ra.y_off = h->y_off;
-    ra.gD = gD;
-    ra.gg = gg;
-    ra.grho = grho;
+    adjoint_rows_args(h, ra, ws, rho, gvs, gD, gg, grho);
     return launch_adjoint_rows(ra, h->y_off_h.data(), h->d_off_h.data(), h->stream);
 }
 
@@ -259,18 +236,6 @@ extern "C" int pdplqr_debug_adjoint_rows(pdplqr_handle h, const double *ws, cons
 extern "C" int pdplqr_debug_adjoint_grad(pdplqr_handle h, const double *ws, double *gE, double *gc, double *gH,
                                          double *gh, double *gx) {
     if (!h || !ws || !h->adj || !h->Lc || !h->lpc) return fail(PDPLQR_ERR_STATE, "debug_adjoint_grad before adjoint");
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
-    AdjointArgs g;
-    g.sh = h->sh;
-    g.ws = ws;
-    g.v = h->adj->v;
-    g.Lc = h->Lc;
-    g.lpc = h->lpc;
-    g.lpa = h->adj->lpa;
-    g.gE = gE;
-    g.gc = gc;
-    g.gH = gH;
-    g.gh = gh;
-    g.gx = gx;
-    return launch_adjoint_grad(g, h->stream);
+    if (int brc = bind_device(h)) return brc;
+    return launch_adjoint_grad(adjoint_args(h, ws, gE, gc, gH, gh, gx), h->stream);
 }

@@ -437,20 +437,6 @@ static int launch_admm_update(const AdmmArgs &a, int lps, bool fuse, bool check,
     return PDPLQR_OK;
 }
 
-template <typename X>
-static int aalloc(pdplqr_handle h, X **p, size_t count) {
-    *p = nullptr;
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(X));
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
-        return PDPLQR_ERR_ALLOC;
-    }
-    h->allocs.push_back(q);
-    *p = reinterpret_cast<X *>(q);
-    return PDPLQR_OK;
-}
-
 static int admm_alloc(pdplqr_handle h) {
     if (h->admm) return PDPLQR_OK;
     AdmmState *s = new AdmmState();
@@ -458,12 +444,12 @@ static int admm_alloc(pdplqr_handle h) {
     const Shape &sh = h->sh;
     const long long B = sh.batch, W = B * sh.perh, Y = B * sh.ny;
     int rc;
-    if ((rc = aalloc(h, &s->wt, W)) || (rc = aalloc(h, &s->w, W)) || (rc = aalloc(h, &s->y, Y)) ||
-        (rc = aalloc(h, &s->z, Y)) || (rc = aalloc(h, &s->lb, Y)) || (rc = aalloc(h, &s->ub, Y)) ||
-        (rc = aalloc(h, &s->rho, Y)) || (rc = aalloc(h, &s->irho, Y)) ||
-        (rc = aalloc(h, &s->x0, B * sh.n)) || (rc = aalloc(h, &s->prim, B)) || (rc = aalloc(h, &s->dual, B)) ||
-        (rc = aalloc(h, &s->done, B)) || (rc = aalloc(h, &s->iters, B)) ||
-        (rc = aalloc(h, &s->conv, B)) || (rc = aalloc(h, &s->active, 2)) || (rc = aalloc(h, &s->rscale, B)))
+    if ((rc = dev_alloc(h, &s->wt, W)) || (rc = dev_alloc(h, &s->w, W)) || (rc = dev_alloc(h, &s->y, Y)) ||
+        (rc = dev_alloc(h, &s->z, Y)) || (rc = dev_alloc(h, &s->lb, Y)) || (rc = dev_alloc(h, &s->ub, Y)) ||
+        (rc = dev_alloc(h, &s->rho, Y)) || (rc = dev_alloc(h, &s->irho, Y)) ||
+        (rc = dev_alloc(h, &s->x0, B * sh.n)) || (rc = dev_alloc(h, &s->prim, B)) || (rc = dev_alloc(h, &s->dual, B)) ||
+        (rc = dev_alloc(h, &s->done, B)) || (rc = dev_alloc(h, &s->iters, B)) ||
+        (rc = dev_alloc(h, &s->conv, B)) || (rc = dev_alloc(h, &s->active, 2)) || (rc = dev_alloc(h, &s->rscale, B)))
         return rc;
     PDPLQR_HIP_TRY(hipHostMalloc((void **)&s->active_h, 2 * sizeof(int32_t), hipHostMallocDefault));
     return PDPLQR_OK;
@@ -476,26 +462,27 @@ void admm_release(pdplqr_handle h) {
     h->admm = nullptr;
 }
 
-// admm_solve on a num_devices > 1 handle (multidev.hip): the ADMM vectors and
-// the update pass live on the first device; every x-update is the reference
-// protocol on the slices -- update_problem_data, then backward (iteration 1 and
-// after a rho change) or backward_without_factorization (its exchange is the
-// slices' (f, p) only), then forward -- with device pointers on the first
-// device (the slices copy their rows peer-to-peer).  The update pass is
-// k_admm_update (the unfused form: h~, g are re-formed by the next
-// update_problem_data on the slices).
-static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const double *x0, const double *lb,
-                         const double *ub, const double *rho, double *ws, double *ys, double *zs, int mem) {
+// the uniform row layout of AdmmArgs::uni: c0 > 0 rows at every stage k < N, none at the terminal
+static int uniform_rows(pdplqr_handle h) {
     const Shape &sh = h->sh;
-    const int dev0 = md_primary_device(h);
-    hipStream_t S = reinterpret_cast<hipStream_t>(md_stream(h));
-    PDPLQR_HIP_TRY(hipSetDevice(dev0));
-    int rc = admm_alloc(h);
-    if (rc) return rc;
+    const int c0 = sh.N > 0 ? h->ncs[0] : 0;
+    bool uni = c0 > 0 && h->ncs[sh.N] == 0;
+    for (int k = 0; k < sh.N && uni; ++k) uni = h->ncs[k] == c0;
+    return uni ? c0 : 0;
+}
+
+// ---------------------------------------------------------------------------
+// The frame of an admm_solve, shared by the single-device loop
+// (pdplqr_admm_solve) and the num_devices one (md_admm_solve): the ADMM state
+// lives on one device, S is the stream it runs on.
+// ---------------------------------------------------------------------------
+// the call's vectors into the state (copy kind `kin`), the input check,
+// irho = 1 / rho and the per-problem resets
+static int admm_begin(pdplqr_handle h, hipStream_t S, hipMemcpyKind kin, const double *x0, const double *lb,
+                      const double *ub, const double *rho, const double *ws, const double *ys, const double *zs) {
     AdmmState *s = h->admm;
+    const Shape &sh = h->sh;
     const long long B = sh.batch, W = B * sh.perh, Y = B * sh.ny;
-    const hipMemcpyKind kin = mem == PDPLQR_MEM_DEVICE ? hipMemcpyDefault : hipMemcpyHostToDevice;
-    if (mem == PDPLQR_MEM_DEVICE) PDPLQR_HIP_TRY(hipDeviceSynchronize());  // inputs made on another stream
     PDPLQR_HIP_TRY(hipMemcpyAsync(s->w, ws, W * sizeof(double), kin, S));
     PDPLQR_HIP_TRY(hipMemcpyAsync(s->x0, x0, B * sh.n * sizeof(double), kin, S));
     if (Y > 0) {
@@ -522,12 +509,15 @@ static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const 
     PDPLQR_HIP_TRY(hipMemsetAsync(s->iters, 0, B * sizeof(int32_t), S));
     PDPLQR_HIP_TRY(hipMemsetAsync(s->prim, 0, B * sizeof(double), S));
     PDPLQR_HIP_TRY(hipMemsetAsync(s->dual, 0, B * sizeof(double), S));
-    PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    return PDPLQR_OK;
+}
+
+// the update pass's arguments both loops share; the caller sets the model side
+// (D, hv, d_off, y_off), the fused outputs (hw, gw) and no_penalty
+static AdmmArgs admm_args(pdplqr_handle h, const pdplqr_admm_settings *st) {
+    AdmmState *s = h->admm;
     AdmmArgs a;
-    a.sh = sh;
-    md_admm_view(h, &a.D, &a.d_off, &a.y_off);
-    a.hv = nullptr;  // (unfused: h~ and g are re-formed by update_problem_data)
-    a.hw = a.gw = nullptr;
+    a.sh = h->sh;
     a.wt = s->wt;
     a.lb = s->lb;
     a.ub = s->ub;
@@ -550,14 +540,82 @@ static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const 
     a.eps_abs = st->eps_abs;
     a.eps_rel = st->eps_rel;
     a.max_nc = h->max_nc;
-    a.no_penalty = 0;
-    {
-        const int c0 = sh.N > 0 ? h->ncs[0] : 0;
-        bool uni = c0 > 0 && h->ncs[sh.N] == 0;
-        for (int k = 0; k < sh.N && uni; ++k) uni = h->ncs[k] == c0;
-        a.uni = uni ? c0 : 0;
+    a.it = 0;
+    a.uni = uniform_rows(h);
+    return a;
+}
+
+// no constraint rows, nothing to split: the one LQ solve in wt is the answer
+static int admm_trivial_exit(pdplqr_handle h, hipStream_t S) {
+    AdmmState *s = h->admm;
+    const long long B = h->sh.batch;
+    PDPLQR_HIP_TRY(hipMemcpyAsync(s->w, s->wt, B * h->sh.perh * sizeof(double), hipMemcpyDeviceToDevice, S));
+    std::vector<int32_t> one(B, 1);
+    PDPLQR_HIP_TRY(hipMemcpyAsync(s->iters, one.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, S));
+    PDPLQR_HIP_TRY(hipMemcpyAsync(s->conv, one.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, S));
+    PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    return PDPLQR_OK;
+}
+
+// after the update pass of a test iteration: 1 when no problem is left
+// iterating (stop), 0 to go on, < 0 an error.  Some problem's rho moved (and
+// this is not the last iteration): rescale, the next x-update refactors the batch.
+static int admm_check(pdplqr_handle h, hipStream_t S, bool last, bool &refactor, int &rho_updates) {
+    AdmmState *s = h->admm;
+    const long long Y = (long long)h->sh.batch * h->sh.ny;
+    PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, S));
+    PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    if (s->active_h[0] == 0) return 1;
+    if (s->active_h[1] && !last) {
+        hipLaunchKernelGGL(k_admm_rescale, dim3((unsigned)((Y + 255) / 256)), dim3(256), 0, S, Y, h->sh.ny, s->rscale,
+                           s->rho, s->irho);
+        PDPLQR_HIP_TRY(hipGetLastError());
+        refactor = true;
+        ++rho_updates;
     }
-    const dim3 ugrid((unsigned)B), ublk(256);
+    return 0;
+}
+
+// w, y, z back to the caller (copy kind `kout`; the caller synchronises)
+static int admm_end(pdplqr_handle h, hipStream_t S, hipMemcpyKind kout, double *ws, double *ys, double *zs) {
+    AdmmState *s = h->admm;
+    const long long B = h->sh.batch, W = B * h->sh.perh, Y = B * h->sh.ny;
+    PDPLQR_HIP_TRY(hipMemcpyAsync(ws, s->w, W * sizeof(double), kout, S));
+    if (Y > 0) {
+        PDPLQR_HIP_TRY(hipMemcpyAsync(ys, s->y, Y * sizeof(double), kout, S));
+        PDPLQR_HIP_TRY(hipMemcpyAsync(zs, s->z, Y * sizeof(double), kout, S));
+    }
+    return PDPLQR_OK;
+}
+
+// admm_solve on a num_devices > 1 handle (multidev.hip): the ADMM vectors and
+// the update pass live on the first device; every x-update is the reference
+// protocol on the slices -- update_problem_data, then backward (iteration 1 and
+// after a rho change) or backward_without_factorization (its exchange is the
+// slices' (f, p) only), then forward -- with device pointers on the first
+// device (the slices copy their rows peer-to-peer).  The update pass is
+// k_admm_update (the unfused form: h~, g are re-formed by the next
+// update_problem_data on the slices).
+static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const double *x0, const double *lb,
+                         const double *ub, const double *rho, double *ws, double *ys, double *zs, int mem) {
+    const Shape &sh = h->sh;
+    hipStream_t S = reinterpret_cast<hipStream_t>(md_stream(h));
+    if (int brc = bind_device(h)) return brc;
+    int rc = admm_alloc(h);
+    if (rc) return rc;
+    AdmmState *s = h->admm;
+    const long long Y = (long long)sh.batch * sh.ny;
+    if (mem == PDPLQR_MEM_DEVICE) PDPLQR_HIP_TRY(hipDeviceSynchronize());  // inputs made on another stream
+    if ((rc = admm_begin(h, S, mem == PDPLQR_MEM_DEVICE ? hipMemcpyDefault : hipMemcpyHostToDevice, x0, lb, ub, rho,
+                         ws, ys, zs)))
+        return rc;
+    PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    AdmmArgs a = admm_args(h, st);
+    md_admm_view(h, &a.D, &a.d_off, &a.y_off);
+    a.hv = nullptr;  // (unfused: h~ and g are re-formed by update_problem_data)
+    a.hw = a.gw = nullptr;
+    a.no_penalty = 0;
+    const dim3 ugrid((unsigned)sh.batch), ublk(256);
     const double *irho_or_null = Y > 0 ? s->irho : nullptr;
     int it = 1, rho_updates = 0;
     bool refactor = true;
@@ -570,13 +628,9 @@ static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const 
         h->factored = true;
         refactor = false;
         if ((rc = md_forward(h, s->x0, s->wt, PDPLQR_MEM_DEVICE))) return rc;  // (returns with the slices drained)
-        PDPLQR_HIP_TRY(hipSetDevice(dev0));
-        if (Y == 0) {  // nothing to split: one LQ solve is the answer
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->w, s->wt, W * sizeof(double), hipMemcpyDeviceToDevice, S));
-            std::vector<int32_t> one(B, 1);
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->iters, one.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, S));
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->conv, one.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, S));
-            PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+        if (int brc = bind_device(h)) return brc;
+        if (Y == 0) {
+            if ((rc = admm_trivial_exit(h, S))) return rc;
             break;
         }
         const bool last = it >= st->max_iter;
@@ -585,42 +639,21 @@ static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const 
         if (check) PDPLQR_HIP_TRY(hipMemsetAsync(s->active, 0, 2 * sizeof(int32_t), S));
         if ((rc = launch_admm_update(a, admm_lps(sh), false, check, ugrid, ublk, S)))
             return rc;
-        if (check) {
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, S));
-            PDPLQR_HIP_TRY(hipStreamSynchronize(S));
-            if (s->active_h[0] == 0) break;
-            if (s->active_h[1] && !last) {
-                hipLaunchKernelGGL(k_admm_rescale, dim3((unsigned)((Y + 255) / 256)), dim3(256), 0, S, Y, sh.ny,
-                                   s->rscale, s->rho, s->irho);
-                PDPLQR_HIP_TRY(hipGetLastError());
-                refactor = true;
-                ++rho_updates;
-            }
+        if (check && (rc = admm_check(h, S, last, refactor, rho_updates))) {
+            if (rc < 0) return rc;
+            break;
         }
         if (last) break;
         PDPLQR_HIP_TRY(hipStreamSynchronize(S));  // the next update reads w, y, z on the slices' streams
     }
-    const hipMemcpyKind kout = mem == PDPLQR_MEM_DEVICE ? hipMemcpyDefault : hipMemcpyDeviceToHost;
-    PDPLQR_HIP_TRY(hipMemcpyAsync(ws, s->w, W * sizeof(double), kout, S));
-    if (Y > 0) {
-        PDPLQR_HIP_TRY(hipMemcpyAsync(ys, s->y, Y * sizeof(double), kout, S));
-        PDPLQR_HIP_TRY(hipMemcpyAsync(zs, s->z, Y * sizeof(double), kout, S));
-    }
+    if ((rc = admm_end(h, S, mem == PDPLQR_MEM_DEVICE ? hipMemcpyDefault : hipMemcpyDeviceToHost, ws, ys, zs)))
+        return rc;
     PDPLQR_HIP_TRY(hipStreamSynchronize(S));
     h->admm_iters = it;
     h->admm_rho_updates = rho_updates;
     s->solved_once = true;
     s->detect_last = false;
     return PDPLQR_OK;
-}
-
-// the uniform row layout of AdmmArgs::uni: c0 > 0 rows at every stage k < N, none at the terminal
-static int uniform_rows(pdplqr_handle h) {
-    const Shape &sh = h->sh;
-    const int c0 = sh.N > 0 ? h->ncs[0] : 0;
-    bool uni = c0 > 0 && h->ncs[sh.N] == 0;
-    for (int k = 0; k < sh.N && uni; ++k) uni = h->ncs[k] == c0;
-    return uni ? c0 : 0;
 }
 
 // why infeasibility detection does not serve this handle (nullptr: it does)
@@ -655,8 +688,8 @@ static int infeas_alloc(pdplqr_handle h) {
     const Shape &sh = h->sh;
     const long long B = sh.batch;
     int rc;
-    if ((rc = aalloc(h, &s->wp, B * sh.perh)) || (rc = aalloc(h, &s->meas, B * 8)) ||
-        (rc = aalloc(h, &s->istat, B)) || (rc = aalloc(h, &s->yp, B * sh.ny)))
+    if ((rc = dev_alloc(h, &s->wp, B * sh.perh)) || (rc = dev_alloc(h, &s->meas, B * 8)) ||
+        (rc = dev_alloc(h, &s->istat, B)) || (rc = dev_alloc(h, &s->yp, B * sh.ny)))
         return rc;
     return PDPLQR_OK;
 }
@@ -726,39 +759,15 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
         return PDPLQR_ERR_INVALID;
     }
     if (h->md) return md_admm_solve(h, st, x0, lb, ub, rho, ws, ys, zs, mem);
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     int rc = admm_alloc(h);
     if (rc) return rc;
     AdmmState *s = h->admm;
     hipStream_t S = h->stream;
-    const long long B = sh.batch, W = B * sh.perh, Y = B * sh.ny;
-    const hipMemcpyKind kin = mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    PDPLQR_HIP_TRY(hipMemcpyAsync(s->w, ws, W * sizeof(double), kin, S));
-    PDPLQR_HIP_TRY(hipMemcpyAsync(s->x0, x0, B * sh.n * sizeof(double), kin, S));
-    if (Y > 0) {
-        PDPLQR_HIP_TRY(hipMemcpyAsync(s->y, ys, Y * sizeof(double), kin, S));
-        PDPLQR_HIP_TRY(hipMemcpyAsync(s->z, zs, Y * sizeof(double), kin, S));
-        PDPLQR_HIP_TRY(hipMemcpyAsync(s->lb, lb, Y * sizeof(double), kin, S));
-        PDPLQR_HIP_TRY(hipMemcpyAsync(s->ub, ub, Y * sizeof(double), kin, S));
-        PDPLQR_HIP_TRY(hipMemcpyAsync(s->rho, rho, Y * sizeof(double), kin, S));
-        PDPLQR_HIP_TRY(hipMemsetAsync(s->active, 0, 2 * sizeof(int32_t), S));
-        hipLaunchKernelGGL(k_admm_validate, dim3((unsigned)((Y + 255) / 256)), dim3(256), 0, S, Y, s->lb, s->ub,
-                           s->rho, s->active);
-        hipLaunchKernelGGL(k_admm_init, dim3((unsigned)((Y + 255) / 256)), dim3(256), 0, S, Y, s->rho, s->irho);
-        PDPLQR_HIP_TRY(hipGetLastError());
-        PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, sizeof(int32_t), hipMemcpyDeviceToHost, S));
-        PDPLQR_HIP_TRY(hipStreamSynchronize(S));
-        if (s->active_h[0] != 0) {
-            set_error("admm_solve: " + std::to_string(s->active_h[0]) +
-                      " constraint rows with e_lb > e_ub, or rho not in (0, inf)");
-            return PDPLQR_ERR_INVALID;
-        }
-    }
-    PDPLQR_HIP_TRY(hipMemsetAsync(s->done, 0, B * sizeof(int32_t), S));
-    PDPLQR_HIP_TRY(hipMemsetAsync(s->conv, 0, B * sizeof(int32_t), S));
-    PDPLQR_HIP_TRY(hipMemsetAsync(s->iters, 0, B * sizeof(int32_t), S));
-    PDPLQR_HIP_TRY(hipMemsetAsync(s->prim, 0, B * sizeof(double), S));
-    PDPLQR_HIP_TRY(hipMemsetAsync(s->dual, 0, B * sizeof(double), S));
+    const long long B = sh.batch, Y = B * sh.ny;
+    if ((rc = admm_begin(h, S, mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, x0, lb, ub,
+                         rho, ws, ys, zs)))
+        return rc;
     // infeasibility detection (off: nothing below launches or copies anything new)
     const bool detect = h->infeas_on != 0;
     const bool det_p = detect && Y > 0 && h->eps_prim_inf > 0.0, det_d = detect && Y > 0 && h->eps_dual_inf > 0.0;
@@ -787,47 +796,17 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
     s->detect_last = detect;
 
     const bool kkt = h->cfg.solver == PDPLQR_SOLVER_KKT;
-    AdmmArgs a;
-    a.sh = sh;
+    AdmmArgs a = admm_args(h, st);
     a.D = h->D;
     a.hv = h->h;
-    a.wt = s->wt;
-    a.lb = s->lb;
-    a.ub = s->ub;
-    a.rho = s->rho;
-    a.irho = s->irho;
-    a.w = s->w;
-    a.y = s->y;
-    a.z = s->z;
     a.hw = h->hw;
     a.gw = h->gw;
     a.d_off = h->d_off;
     a.y_off = h->y_off;
-    a.done = s->done;
-    a.iters = s->iters;
-    a.conv = s->conv;
-    a.active = s->active;
-    a.prim = s->prim;
-    a.dual = s->dual;
-    a.rscale = s->rscale;
-    a.adaptive = st->adaptive_rho ? 1 : 0;
-    a.rho_tol = st->adaptive_rho_tolerance;
-    a.alpha = st->alpha;
-    a.sigma = st->sigma;
-    a.eps_abs = st->eps_abs;
-    a.eps_rel = st->eps_rel;
-    a.max_nc = h->max_nc;
-    a.it = 0;
     // KKT with the factor cache: the update pass also forms the next h~ = h - sigma w
     // and g (the KKT path takes rho through g in its backward, no penalty in h~)
     const bool kkt_lin = kkt && kkt_linear_supported(h);
     a.no_penalty = kkt ? 1 : 0;
-    {
-        const int c0 = sh.N > 0 ? h->ncs[0] : 0;
-        bool uni = c0 > 0 && h->ncs[sh.N] == 0;
-        for (int k = 0; k < sh.N && uni; ++k) uni = h->ncs[k] == c0;
-        a.uni = uni ? c0 : 0;
-    }
     const dim3 ugrid((unsigned)B), ublk(256);
     const double *irho_or_null = Y > 0 ? s->irho : nullptr;
     int it = 1;
@@ -872,17 +851,9 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
             if (check) PDPLQR_HIP_TRY(hipMemsetAsync(s->active, 0, 2 * sizeof(int32_t), S));
             rc = kkt_forward_admm(h, s->x0, a, fuse, check);
             if (rc == PDPLQR_OK) {
-                if (check) {
-                    PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, S));
-                    PDPLQR_HIP_TRY(hipStreamSynchronize(S));
-                    if (s->active_h[0] == 0) break;
-                    if (s->active_h[1] && !last) {
-                        hipLaunchKernelGGL(k_admm_rescale, dim3((unsigned)((Y + 255) / 256)), dim3(256), 0, S, Y, sh.ny,
-                                           s->rscale, s->rho, s->irho);
-                        PDPLQR_HIP_TRY(hipGetLastError());
-                        refactor = true;
-                        ++rho_updates;
-                    }
+                if (check && (rc = admm_check(h, S, last, refactor, rho_updates))) {
+                    if (rc < 0) return rc;
+                    break;
                 }
                 if (last) break;
                 continue;
@@ -891,12 +862,8 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
             can_fuse_kkt = false;
         }
         if ((rc = solver_forward(h, s->x0, s->wt))) return rc;
-        if (Y == 0) {  // nothing to split: one LQ solve is the answer
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->w, s->wt, W * sizeof(double), hipMemcpyDeviceToDevice, S));
-            std::vector<int32_t> one(B, 1);
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->iters, one.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, S));
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->conv, one.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, S));
-            PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+        if (Y == 0) {
+            if ((rc = admm_trivial_exit(h, S))) return rc;
             break;
         }
         if (check) PDPLQR_HIP_TRY(hipMemsetAsync(s->active, 0, 2 * sizeof(int32_t), S));
@@ -917,28 +884,18 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
             // (solved takes precedence); a certified one leaves `active`
             if (det_p && (rc = launch_infeas_primal(q, S))) return rc;
             if (det_d && (rc = launch_infeas_dual(q, S))) return rc;
-            PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, S));
-            PDPLQR_HIP_TRY(hipStreamSynchronize(S));
-            if (s->active_h[0] == 0) break;
-            if (s->active_h[1] && !last) {  // some problem's rho moved: rescale, refactor the batch
-                hipLaunchKernelGGL(k_admm_rescale, dim3((unsigned)((Y + 255) / 256)), dim3(256), 0, S, Y, sh.ny,
-                                   s->rscale, s->rho, s->irho);
-                PDPLQR_HIP_TRY(hipGetLastError());
-                refactor = true;
-                fused = false;  // the fused backward used the old rho: refactor instead
-                ++rho_updates;
+            if ((rc = admm_check(h, S, last, refactor, rho_updates))) {
+                if (rc < 0) return rc;
+                break;
             }
+            if (refactor) fused = false;  // the fused backward used the old rho: refactor instead
         }
         if (last) break;
     }
     // fused iterations leave h~/g of the NEXT x-update in the workspace; the
     // protocol state is "updated and factored" either way
-    const hipMemcpyKind kout = mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    PDPLQR_HIP_TRY(hipMemcpyAsync(ws, s->w, W * sizeof(double), kout, S));
-    if (Y > 0) {
-        PDPLQR_HIP_TRY(hipMemcpyAsync(ys, s->y, Y * sizeof(double), kout, S));
-        PDPLQR_HIP_TRY(hipMemcpyAsync(zs, s->z, Y * sizeof(double), kout, S));
-    }
+    if ((rc = admm_end(h, S, mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ws, ys, zs)))
+        return rc;
     if (mem != PDPLQR_MEM_DEVICE) PDPLQR_HIP_TRY(hipStreamSynchronize(S));
     h->hw_cached = false;
     h->admm_iters = it;
@@ -953,7 +910,7 @@ int pdplqr_admm_info(pdplqr_handle h, int32_t *iters, int32_t *converged, double
         set_error("admm_info before admm_solve");
         return PDPLQR_ERR_STATE;
     }
-    PDPLQR_HIP_TRY(hipSetDevice(h->md ? md_primary_device(h) : h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     PDPLQR_HIP_TRY(hipStreamSynchronize(h->md ? reinterpret_cast<hipStream_t>(md_stream(h)) : h->stream));
     AdmmState *s = h->admm;
     const size_t B = (size_t)h->sh.batch;
@@ -992,7 +949,7 @@ int pdplqr_admm_status(pdplqr_handle h, int32_t *status) {
         set_error("admm_status before admm_solve");
         return PDPLQR_ERR_STATE;
     }
-    PDPLQR_HIP_TRY(hipSetDevice(h->md ? md_primary_device(h) : h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     PDPLQR_HIP_TRY(hipStreamSynchronize(h->md ? reinterpret_cast<hipStream_t>(md_stream(h)) : h->stream));
     AdmmState *s = h->admm;
     const size_t B = (size_t)h->sh.batch;
@@ -1012,7 +969,7 @@ int pdplqr_admm_certificate(pdplqr_handle h, double *dy, double *dw, int mem) {
         set_error("admm_certificate: the last admm_solve did not run with infeasibility detection on");
         return PDPLQR_ERR_STATE;
     }
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     AdmmState *s = h->admm;
     hipStream_t S = h->stream;
     const Shape &sh = h->sh;
@@ -1054,7 +1011,7 @@ int pdplqr_admm_check_certificates(pdplqr_handle h, const double *x0, const doub
         set_error("admm_check_certificates: null x0 / lb / ub");
         return PDPLQR_ERR_INVALID;
     }
-    PDPLQR_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int brc = bind_device(h)) return brc;
     hipStream_t S = h->stream;
     const size_t B = (size_t)sh.batch, W = B * sh.perh, Y = B * sh.ny;
     int rc;

@@ -20,7 +20,7 @@ extern "C" int pdplqr_debug_combine_form(int n, const double *a, const double *b
     using namespace pdplqr;
     const int T = n <= 16 ? 1 : (n <= 32 ? 2 : (n <= 64 ? 4 : 0));  // 4: the LDS kernels (kernels_wide.hip)
     if (!T) return PDPLQR_ERR_UNSUPPORTED;
-    const size_t es = (size_t)(3 * n * n + 2 * n) * sizeof(double);
+    const size_t es = (size_t)elem_doubles(n) * sizeof(double);
     double *d = nullptr;
     int *dok = nullptr, okh = 0;
     PDPLQR_HIP_TRY(hipMalloc(&d, 3 * es));
@@ -69,7 +69,7 @@ extern "C" int pdplqr_debug_combine_mw(int n, const double *a, const double *b, 
     using namespace pdplqr;
     const int T = n <= 16 ? 1 : (n <= 32 ? 2 : 0);
     if (!T) return PDPLQR_ERR_UNSUPPORTED;
-    const size_t es = (size_t)(3 * n * n + 2 * n) * sizeof(double);
+    const size_t es = (size_t)elem_doubles(n) * sizeof(double);
     double *d = nullptr;
     int *dok = nullptr, okh = 0;
     PDPLQR_HIP_TRY(hipMalloc(&d, 3 * es));
@@ -79,7 +79,7 @@ extern "C" int pdplqr_debug_combine_mw(int n, const double *a, const double *b, 
     PDPLQR_HIP_TRY(hipMemcpy((char *)d + 2 * es, out, es, hipMemcpyHostToDevice));  // untouched blocks kept
     const double *da = d, *db = (const double *)((char *)d + es);
     double *dout = (double *)((char *)d + 2 * es);
-    const size_t sm = (size_t)((mw_smem_bytes(n) + 15) / 16 * 2 + 2 * ((3 * n * n + 2 * n + 1) & ~1)) * sizeof(double);
+    const size_t sm = (size_t)((mw_smem_bytes(n) + 15) / 16 * 2 + 2 * ((elem_doubles(n) + 1) & ~1LL)) * sizeof(double);
     if (T == 1) hipLaunchKernelGGL(k_debug_combine_mw<1>, dim3(1), dim3(256), sm, 0, da, db, dout, n, fcf, dok);
     else hipLaunchKernelGGL(k_debug_combine_mw<2>, dim3(1), dim3(256), sm, 0, da, db, dout, n, fcf, dok);
     PDPLQR_HIP_TRY(hipDeviceSynchronize());
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void k_debug_combine_qd(const double *a, const
 extern "C" int pdplqr_debug_combine_qd(const double *a, const double *b, double *out, int fcf) {
     using namespace pdplqr;
     constexpr int n = QD_N;
-    const size_t es = (size_t)(3 * n * n + 2 * n) * sizeof(double);
+    const size_t es = (size_t)elem_doubles(n) * sizeof(double);
     double *d = nullptr;
     int *dok = nullptr, okh = 0;
     PDPLQR_HIP_TRY(hipMalloc(&d, 3 * es));
@@ -119,7 +119,7 @@ extern "C" int pdplqr_debug_combine_qd(const double *a, const double *b, double 
     PDPLQR_HIP_TRY(hipMemcpy((char *)d + 2 * es, out, es, hipMemcpyHostToDevice));  // untouched blocks kept
     const double *da = d, *db = (const double *)((char *)d + es);
     double *dout = (double *)((char *)d + 2 * es);
-    const size_t sm = (size_t)(qd_smem_doubles() + 2 + 2 * ((3 * n * n + 2 * n + 1) & ~1)) * sizeof(double);
+    const size_t sm = (size_t)(qd_smem_doubles() + 2 + 2 * ((elem_doubles(n) + 1) & ~1LL)) * sizeof(double);
     hipLaunchKernelGGL(k_debug_combine_qd, dim3(1), dim3(256), sm, 0, da, db, dout, fcf, dok);
     PDPLQR_HIP_TRY(hipDeviceSynchronize());
     PDPLQR_HIP_TRY(hipMemcpy(out, dout, es, hipMemcpyDeviceToHost));
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(64) void k_debug_combine_qd1(const double *a, const
 extern "C" int pdplqr_debug_combine_qd1(int n, const double *a, const double *b, double *out, int fcf) {
     using namespace pdplqr;
     if (n != 4 && n != 8 && n != 12) return PDPLQR_ERR_INVALID;
-    const size_t es = (size_t)(3 * n * n + 2 * n) * sizeof(double);
+    const size_t es = (size_t)elem_doubles(n) * sizeof(double);
     double *d = nullptr;
     int *dok = nullptr, okh = 0;
     PDPLQR_HIP_TRY(hipMalloc(&d, 3 * es));

@@ -84,6 +84,10 @@ __host__ __device__ inline long long kkt_xl_ws_doubles(const Shape &sh) {
     return (long long)sh.n * sh.s + 2LL * sh.n * sh.n + (long long)sh.s * sh.s;
 }
 
+// doubles of one segment element (F, C, P | f, p) and of one boundary map (Phi | phi)
+__host__ __device__ inline long long elem_doubles(int n) { return 3LL * n * n + 2LL * n; }
+__host__ __device__ inline long long map_doubles(int n) { return (long long)n * n + n; }
+
 int launch_riccati_backward_xl(const RiccatiArgs &a, hipStream_t st);
 int launch_riccati_backward_nofact_xl(const RiccatiArgs &a, hipStream_t st);
 int launch_riccati_forward_xl(const Shape &sh, const double *E, const double *c, const double *FR, const double *x0,
@@ -169,7 +173,7 @@ struct pdplqr_handle_s {
     long long model_upload_bytes = 0;  // host -> device model bytes (pdplqr_get_model_upload_bytes)
     bool host_staged = false;  // a host->device copy is in flight on `stream`
     std::vector<void *> allocs;
-    pdplqr::ParallelState *par = nullptr;  // PARALLEL solver state (solvers.hip)
+    pdplqr::ParallelState *par = nullptr;  // PARALLEL solver state (parallel_host.hip)
     pdplqr::KKTState *kkt = nullptr;       // KKT solver state (kkt.hip)
     pdplqr::AdmmState *admm = nullptr;     // ADMM outer loop state (admm.hip), allocated on first use
     pdplqr::AdjointState *adj = nullptr;   // pdplqr_adjoint scratch (adjoint.hip), allocated on first use
@@ -188,3 +192,28 @@ struct pdplqr_handle_s {
         hipStream_t stream = nullptr;
     } graphs[3];
 };
+
+// Host helpers shared by the host files (defined in abi.hip).
+namespace pdplqr {
+// hipMalloc of `bytes`, recorded in h->allocs (freed with the handle)
+int dev_alloc_bytes(pdplqr_handle h, void **p, size_t bytes);
+// `count` X on the handle's device, freed with the handle; a count of 0 allocates one
+template <typename X>
+inline int dev_alloc(pdplqr_handle h, X **p, size_t count) {
+    *p = nullptr;
+    void *q = nullptr;
+    const int rc = dev_alloc_bytes(h, &q, (count ? count : 1) * sizeof(X));
+    *p = reinterpret_cast<X *>(q);
+    return rc;
+}
+// Makes the handle's device current (a num_devices handle: its first device); ERR_HIP on failure.
+int bind_device(pdplqr_handle h);
+// Copies `count` doubles from host or device memory into device buffer `dst`
+// (or returns the device pointer itself when no copy is needed).
+int stage_in(pdplqr_handle h, const double *src, double *dst, long long count, int mem, const double **out);
+// Host memory: copies `count` doubles of device buffer `src` to `dst` and waits
+// for the stream (no host->device copy is in flight after it).  Device memory:
+// nothing, the kernels wrote `dst` itself.
+int stage_out(pdplqr_handle h, double *dst, const double *src, long long count, int mem);
+RiccatiArgs riccati_args(pdplqr_handle h);  // the serial kernels' arguments from the handle
+}  // namespace pdplqr

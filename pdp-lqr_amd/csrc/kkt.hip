@@ -1172,20 +1172,6 @@ struct KKTState {
     double *xlw = nullptr;     // KKT_RIC_XL: per-problem workspace (kernels_xl.hip)
 };
 
-template <typename X>
-static int kalloc(pdplqr_handle h, X **p, size_t count) {
-    *p = nullptr;
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(X));
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
-        return PDPLQR_ERR_ALLOC;
-    }
-    h->allocs.push_back(q);
-    *p = reinterpret_cast<X *>(q);
-    return PDPLQR_OK;
-}
-
 static KKTArgs kkt_args(pdplqr_handle h) {
     KKTState *ks = h->kkt;
     KKTArgs a;
@@ -1244,8 +1230,8 @@ int kkt_init(pdplqr_handle h) {
     int rc;
     ks->ric = kkt_ric_nc(sh, h->ncs, dmax <= 32);
     if (ks->ric >= 0) {  // Riccati-ordered path: no tile buffers
-        if ((rc = kalloc(h, &ks->rec, B * kkt_ric_rec_doubles(sh, ks->ric))) || (rc = kalloc(h, &ks->x0acc, B * n)) ||
-            (ks->ric == KKT_RIC_XL && (rc = kalloc(h, &ks->xlw, B * kkt_xl_ws_doubles(sh)))))
+        if ((rc = dev_alloc(h, &ks->rec, B * kkt_ric_rec_doubles(sh, ks->ric))) || (rc = dev_alloc(h, &ks->x0acc, B * n)) ||
+            (ks->ric == KKT_RIC_XL && (rc = dev_alloc(h, &ks->xlw, B * kkt_xl_ws_doubles(sh)))))
             return rc;
         PDPLQR_HIP_TRY(hipMemset(ks->x0acc, 0, B * n * sizeof(double)));
         return PDPLQR_OK;
@@ -1270,14 +1256,14 @@ int kkt_init(pdplqr_handle h) {
             for (int q = 0; q < h->ncs[k]; ++q) rows[base + n + q] = make_int4(1, k, q, 0);
         }
     }
-    if ((rc = kalloc(h, &ks->d_prim_off, N + 1)) || (rc = kalloc(h, &ks->d_prim_dim, N + 1)) ||
-        (rc = kalloc(h, &ks->d_dual_off, N + 1)) || (rc = kalloc(h, &ks->d_gdim, N + 1)) ||
-        (rc = kalloc(h, &ks->d_ncs, N + 1)) || (rc = kalloc(h, &ks->rows, ks->dim)) || (rc = kalloc(h, &ks->pstat, B)) ||
-        (rc = kalloc(h, &ks->blk, B * (N + 1) * 6 * PP)) || (rc = kalloc(h, &ks->fac, B * (N + 1) * 3 * PP)) ||
-        (rc = kalloc(h, &ks->rhs, B * ks->dim)) ||
-        (ks->P == 16 && ((rc = kalloc(h, &ks->dpk, B * (N + 1) * 512)) || (rc = kalloc(h, &ks->dreg, B * (N + 1) * 16)) ||
-                         (rc = kalloc(h, &ks->bvec, B * (N + 1) * 16)) ||
-                         (rc = kalloc(h, &ks->ppk, B * (N + 1) * PPK)))) || (rc = kalloc(h, &ks->wv, B * (N + 1) * 4 * ks->P)))
+    if ((rc = dev_alloc(h, &ks->d_prim_off, N + 1)) || (rc = dev_alloc(h, &ks->d_prim_dim, N + 1)) ||
+        (rc = dev_alloc(h, &ks->d_dual_off, N + 1)) || (rc = dev_alloc(h, &ks->d_gdim, N + 1)) ||
+        (rc = dev_alloc(h, &ks->d_ncs, N + 1)) || (rc = dev_alloc(h, &ks->rows, ks->dim)) || (rc = dev_alloc(h, &ks->pstat, B)) ||
+        (rc = dev_alloc(h, &ks->blk, B * (N + 1) * 6 * PP)) || (rc = dev_alloc(h, &ks->fac, B * (N + 1) * 3 * PP)) ||
+        (rc = dev_alloc(h, &ks->rhs, B * ks->dim)) ||
+        (ks->P == 16 && ((rc = dev_alloc(h, &ks->dpk, B * (N + 1) * 512)) || (rc = dev_alloc(h, &ks->dreg, B * (N + 1) * 16)) ||
+                         (rc = dev_alloc(h, &ks->bvec, B * (N + 1) * 16)) ||
+                         (rc = dev_alloc(h, &ks->ppk, B * (N + 1) * PPK)))) || (rc = dev_alloc(h, &ks->wv, B * (N + 1) * 4 * ks->P)))
         return rc;
     PDPLQR_HIP_TRY(hipMemcpy(ks->d_prim_off, ks->prim_off.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
     PDPLQR_HIP_TRY(hipMemcpy(ks->d_prim_dim, ks->prim_dim.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1337,8 +1323,8 @@ int kkt_before_model(pdplqr_handle h) {
     if (!ks || ks->ric < 0 || !ks->formed || ks->Ef) return PDPLQR_OK;
     const Shape &sh = h->sh;
     int rc;
-    if ((rc = kalloc(h, &ks->Ef, sh.batch * sh.perE)) ||
-        (sh.ndD > 0 && (rc = kalloc(h, &ks->Df, sh.batch * (long long)sh.ndD))))
+    if ((rc = dev_alloc(h, &ks->Ef, sh.batch * sh.perE)) ||
+        (sh.ndD > 0 && (rc = dev_alloc(h, &ks->Df, sh.batch * (long long)sh.ndD))))
         return rc;
     PDPLQR_HIP_TRY(hipMemcpyAsync(ks->Ef, h->E, sh.batch * sh.perE * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     if (sh.ndD > 0)
@@ -1401,7 +1387,7 @@ int kkt_backward_cached(pdplqr_handle h, const double *inv_rho) {
     KKTState *ks = h->kkt;
     const Shape &sh = h->sh;
     int rc;
-    if (!ks->ncache && (rc = kalloc(h, &ks->ncache, sh.batch * kkt_ric_cache_doubles(sh, ks->ric)))) return rc;
+    if (!ks->ncache && (rc = dev_alloc(h, &ks->ncache, sh.batch * kkt_ric_cache_doubles(sh, ks->ric)))) return rc;
     h->rec_gain = false;  // the cache-writing backward leaves the P~ record (pdplqr_handle_s::rec_gain)
     rc = launch_kkt_ric_backward(sh, ks->ric, ks->Ef ? ks->Ef : h->E, h->c, ks->Df ? ks->Df : h->D, h->Hw, h->hw,
                                  h->gw, inv_rho, h->d_off, h->y_off, h->ncs[sh.N], h->cfg.rho_dyn, ks->rec, h->status,

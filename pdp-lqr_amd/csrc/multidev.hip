@@ -3,7 +3,7 @@
 // SURVEY.md 8(b)).  The multi-GPU form of LQRParallelSolver
 // (lqr_solver_parallel.hpp:22-25,142-146,213-238) for a C / C++ caller that has
 // no torch.distributed: each slice is a PARALLEL shard handle on its device
-// (segment backward + local suffix scan -> the slice element, solvers.hip
+// (segment backward + local suffix scan -> the slice element, parallel_host.hip
 // pdplqr_shard_backward); the R elements (3n^2 + 2n doubles per problem) are
 // all-gathered over RCCL (ncclAllGather on ncclCommInitAll communicators, one
 // group call across the devices' streams); each shard then folds the gathered
@@ -256,7 +256,7 @@ int md_create(pdplqr_handle h, const pdplqr_config &C) {
     md->dev = devs;
     md->allocs.resize(R);
     md_plan(C.N, R, h->ncs, C.nx, C.nu, md->plan);
-    const long long B = C.batch, es = 3LL * C.nx * C.nx + 2LL * C.nx;
+    const long long B = C.batch, es = elem_doubles(C.nx);
     const int n = C.nx, s = C.nx + C.nu;
     md->sh.assign(R, nullptr);
     md->st.assign(R, nullptr);
@@ -494,7 +494,7 @@ int md_backward(pdplqr_handle h, const double *rho, int mem, bool fact) {
     MultiDev *md = h->md;
     const Shape &g = h->sh;
     const int N = g.N, Bi = g.batch, n = g.n;
-    const long long es = 3LL * n * n + 2LL * n;
+    const long long es = elem_doubles(n);
     const long long cnt = (long long)Bi * (fact ? es : 2LL * n);
     const hipMemcpyKind kind = md_kind(mem, true);
     int rc;

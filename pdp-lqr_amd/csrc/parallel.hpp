@@ -236,4 +236,29 @@ int launch_rank_fold_maps_xl(const double *elems, const double *suf, const doubl
 int launch_riccati_forward_seg_xl(const Shape &sh, const double *E, const double *c, const double *FR,
                                   const SegFwd &sf, double *ws, hipStream_t st);
 
+// Host side of the PARALLEL solver (parallel_host.hip), as solvers.hip drives it.
+int parallel_init(pdplqr_handle h);      // state, device segments, buffers
+void parallel_release(pdplqr_handle h);
+// segment backward + suffix scan; `last_is_terminal` = 0 for a non-final
+// horizon shard.
+int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact = true);
+// condensed forward: boundary maps under the suffix value functions, their
+// prefix composition (ceil(log2 (S + 1)) rounds), then the segment rollouts
+int parallel_forward(pdplqr_handle h, const double *x0, double *ws, const double *left, const double *right,
+                     int last_is_terminal, long long rstride = 0);
+int parallel_status(pdplqr_handle h, int32_t *flags);  // per-problem status (host)
+
+// The device segments of one problem: every reference segment (num_segments,
+// load_balancing: lqr_solver_parallel.hpp:70-81) cut into pieces of at most
+// segment_len stages, or, for segment_len <= 0, of the length the cost model
+// picks.  slots[f][0] / slots[f][1] are seg_backward_slots / seg_scan_slots
+// with Shape::mw = 1 (f = 0) and 0 (f = 1); `mw` is the family the plan chose.
+// Host arithmetic only.  false: the reference segmentation has an empty segment.
+struct SegPlan {
+    int mw;
+    std::vector<int32_t> start, len;
+};
+bool plan_segments(int N, int n, int m, int batch, int num_segments, bool load_balancing, int segment_len,
+                   const int slots[2][2], SegPlan &out);
+
 }  // namespace pdplqr
