@@ -394,6 +394,64 @@ int pdplqr_admm_check_certificates(pdplqr_handle h, const double *x0, const doub
                                    const double *dy, const double *dw, double eps_prim_inf,
                                    double eps_dual_inf, double *measures, int32_t *verdict, int mem);
 
+/* ---------------------------------------------------------------------- */
+/* Polish of the ADMM solution (new; OSQP's polish, Stellato et al. 2020    */
+/* section 4, with the dynamics kept as hard constraints).   */
+/* admm_solve stops at first-order accuracy (eps); the polish guesses the   */
+/* active rows from (y, z), solves the equality-constrained problem on them */
+/* regularised by delta, and refines: refine_iter + 1 penalised x-updates   */
+/* of the protocol with sigma = delta, rho = 1/delta on the active rows and */
+/* 0 on the rest, zs = the active bounds, each followed by                  */
+/*   y <- y + (D_a w - b_a) / delta.                                        */
+/* Same limits as infeasibility detection (SERIAL and PARALLEL, one device, */
+/* nx + nu <= 64, any ncs, either keep_factors value: with keep_factors = 0 */
+/* every refinement step factorises); PDPLQR_ERR_UNSUPPORTED otherwise.     */
+/* ---------------------------------------------------------------------- */
+#define PDPLQR_POLISH_NOT_ATTEMPTED 0 /* the problem did not end SOLVED           */
+#define PDPLQR_POLISH_ACCEPTED 1      /* the polished (w, y, z) were written back */
+#define PDPLQR_POLISH_REJECTED 2      /* the ADMM iterate is kept, bit for bit    */
+
+/* Polish state of the handle (default: off; with it off admm_solve launches  */
+/* and copies nothing new and its results are unchanged bit for bit).  OSQP's */
+/* defaults: delta = 1e-6, refine_iter = 3.  delta <= 0 or not finite, or      */
+/* refine_iter < 0, with `enable` set is PDPLQR_ERR_INVALID.  With it on,      */
+/* admm_solve, after its loop and on the handle's stream:                      */
+/*   classifies every row: lower-active if lb == ub or z - lb < -y, else       */
+/*     upper-active if ub - z < y (OSQP's rule);                               */
+/*   runs the refinement from (w, y on the active rows, 0 elsewhere);          */
+/*   takes the KKT measures (pdplqr_admm_kkt_residuals) of the ADMM (w, y) and */
+/*     of the polished pair; with pri = max([0], [1]) and dua = [2] the        */
+/*     polished pair is accepted when pri_pol < pri && dua_pol < dua, or       */
+/*     pri_pol < pri && dua < 1e-10, or dua_pol < dua && pri < 1e-10;          */
+/*   an accepted problem gets w, y and z = clamp(D w, lb, ub); a rejected one, */
+/*     one that did not end SOLVED, or one whose polish factorisation failed   */
+/*     keeps its ADMM w, y, z bit for bit.                                     */
+/* pdplqr_admm_info and pdplqr_admm_status are unchanged.  After the call the  */
+/* handle is "updated and factored" for the POLISHING system: a following      */
+/* pdplqr_forward returns the last polish iterate of every problem.            */
+int pdplqr_admm_set_polish(pdplqr_handle h, int enable, double delta, int32_t refine_iter);
+
+/* The polish of the last admm_solve, host arrays, any of them NULL:          */
+/* status [batch] (PDPLQR_POLISH_*), n_active [batch] (rows guessed active),  */
+/* measures [batch][8]: the four KKT measures of the ADMM iterate, then of    */
+/* the polished pair.  PDPLQR_ERR_STATE unless polish was on in that solve.   */
+int pdplqr_admm_polish_info(pdplqr_handle h, int32_t *status, int32_t *n_active, double *measures);
+
+/* The KKT measures of any (w, y), without the loop: needs only set_model,    */
+/* same limits as above; changes no handle state.  x0 [batch][n], lb, ub, ys  */
+/* [batch][ny], ws [batch][N*s+n], measures [batch][4], all pointers in `mem`.*/
+/* With v = D w, |.| the max-norm and a bound with |value| >= 1e20 infinite:  */
+/*   [0] the row residual max_i |v_i - clamp(v_i + y_i, lb_i, ub_i)| (the     */
+/*       natural map: zero iff v is within the bounds and y in their normal   */
+/*       cone -- bound violation, multiplier sign and complementarity in one) */
+/*   [1] the dynamics residual max(|x_0 - x0|, max_k |x_{k+1} - E_k w_k - c_k|)*/
+/*   [2] the reduced gradient max_k |g_k|: nu_N = q_N, [g_k; nu_k] = q_k +    */
+/*       E_k^T nu_{k+1}, q_k = H_k w_k + h_k + D_k^T y_k (the model's H,      */
+/*       without sigma)                                                       */
+/*   [3] the objective sum_k 1/2 w_k^T H_k w_k + h_k^T w_k                    */
+int pdplqr_admm_kkt_residuals(pdplqr_handle h, const double *x0, const double *lb, const double *ub,
+                              const double *ws, const double *ys, double *measures, int mem);
+
 /* Device info helpers (for hosts that do not link HIP). */
 int pdplqr_device_count(int32_t *count);
 

@@ -45,10 +45,14 @@
 //   * the KKT solver re-forms its right-hand side (form_rhs) and re-solves
 //     with the factor of the first iteration (the KKT matrix depends on rho
 //     only, qdldl_solver.hpp:88-109).
+// After the loop, opt-in (pdplqr_admm_set_polish): OSQP's polish (its section
+// 4) as refine_iter + 1 more x-updates of the same protocol on the guessed
+// active rows (admm_polish below, kernels_polish.hip).
 #include <algorithm>
 
 #include "admm.hpp"
 #include "device_common.hpp"
+#include "parallel.hpp"
 #include "solvers.hpp"
 
 namespace pdplqr {
@@ -69,6 +73,12 @@ struct AdmmState {
     int32_t *istat = nullptr;             // [b] 0, or PDPLQR_ADMM_{PRIMAL,DUAL}_INFEASIBLE
     bool solved_once = false;             // an admm_solve ran its loop
     bool detect_last = false;             // the last admm_solve ran with detection on
+    // polish (allocated by the first admm_solve that runs with it on)
+    double *pw = nullptr, *py = nullptr, *pv = nullptr;        // the polish iterate (w, y) and D w
+    double *prho = nullptr, *pirho = nullptr, *pb = nullptr;   // its x-update's rho, inv_rho, row targets
+    double *pmeas = nullptr;                                   // [b][8] KKT measures: ADMM iterate, polished pair
+    int32_t *pstat = nullptr, *pnact = nullptr;                // [b] outcome, rows guessed active
+    bool polish_last = false;                                  // the last admm_solve ran with polish on
 };
 
 // sum over the LPS lanes of one stage (xor butterflies: every lane ends with
@@ -653,6 +663,7 @@ static int md_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const 
     h->admm_rho_updates = rho_updates;
     s->solved_once = true;
     s->detect_last = false;
+    s->polish_last = false;
     return PDPLQR_OK;
 }
 
@@ -717,6 +728,100 @@ struct CallBuf {
         return PDPLQR_OK;
     }
 };
+
+static void kkt_model_args(pdplqr_handle h, KktArgs &q) {
+    q.sh = h->sh;
+    q.E = h->E;
+    q.c = h->c;
+    q.H = h->H;
+    q.hv = h->h;
+    q.D = h->D;
+    q.d_off = h->d_off;
+    q.y_off = h->y_off;
+    q.uni = uniform_rows(h);
+    q.max_nc = h->max_nc;
+}
+
+static int polish_alloc(pdplqr_handle h) {
+    AdmmState *s = h->admm;
+    if (s->pw) return PDPLQR_OK;
+    const Shape &sh = h->sh;
+    const long long B = sh.batch, Y = B * sh.ny;
+    int rc;
+    if ((rc = dev_alloc(h, &s->py, Y)) || (rc = dev_alloc(h, &s->pv, Y)) || (rc = dev_alloc(h, &s->prho, Y)) ||
+        (rc = dev_alloc(h, &s->pirho, Y)) || (rc = dev_alloc(h, &s->pb, Y)) || (rc = dev_alloc(h, &s->pmeas, B * 8)) ||
+        (rc = dev_alloc(h, &s->pstat, B)) || (rc = dev_alloc(h, &s->pnact, B)) ||
+        (rc = dev_alloc(h, &s->pw, B * sh.perh)))
+        return rc;
+    return PDPLQR_OK;
+}
+
+// The polish of admm_solve, after the loop, on the
+// state's (w, y, z): classify, refine_iter + 1 penalised x-updates of the
+// protocol with sigma = delta, rho = 1/delta on the active rows and 0 on the
+// rest (one factorisation; keep_factors = 0: every one factorises), the KKT
+// measures before and after, OSQP's acceptance rule, the write-back.  Nothing
+// here waits for the device.
+static int admm_polish(pdplqr_handle h, hipStream_t S) {
+    AdmmState *s = h->admm;
+    const Shape &sh = h->sh;
+    const long long B = sh.batch, W = B * sh.perh;
+    int rc;
+    PolishArgs p{};
+    p.sh = sh;
+    p.D = h->D;
+    p.lb = s->lb;
+    p.ub = s->ub;
+    p.y = s->y;
+    p.z = s->z;
+    p.d_off = h->d_off;
+    p.y_off = h->y_off;
+    p.uni = uniform_rows(h);
+    p.max_nc = h->max_nc;
+    p.delta = h->polish_delta;
+    p.rho_p = s->prho;
+    p.irho_p = s->pirho;
+    p.bt = s->pb;
+    p.wp = s->pw;
+    p.yp = s->py;
+    p.vp = s->pv;
+    p.nact = s->pnact;
+    KktArgs q{};
+    kkt_model_args(h, q);
+    q.x0 = s->x0;
+    q.lb = s->lb;
+    q.ub = s->ub;
+    q.meas = s->pmeas;
+    q.mstride = 8;
+    if ((rc = launch_polish_classify(p, S))) return rc;
+    PDPLQR_HIP_TRY(hipMemcpyAsync(s->pw, s->w, W * sizeof(double), hipMemcpyDeviceToDevice, S));
+    q.w = s->w;
+    q.y = s->y;
+    if ((rc = launch_kkt_residual(q, S))) return rc;
+    const bool keep = h->Lc != nullptr && h->lpc != nullptr;
+    for (int j = 0; j <= h->polish_refine; ++j) {
+        if ((rc = solver_update(h, s->pw, s->py, s->pb, s->pirho, h->polish_delta))) return rc;
+        h->updated = true;
+        if (j == 0 || !keep) {
+            if ((rc = solver_backward(h, s->prho))) return rc;
+            h->factored = true;
+        } else if ((rc = solver_backward_nofact(h, s->prho))) {
+            return rc;
+        }
+        if ((rc = solver_forward(h, s->x0, s->pw))) return rc;
+        if ((rc = launch_polish_ystep(p, S))) return rc;
+    }
+    q.w = s->pw;
+    q.y = s->py;
+    q.meas = s->pmeas + 4;
+    if ((rc = launch_kkt_residual(q, S))) return rc;
+    // a failed Cholesky of the polish factorisation rejects that problem only
+    const int32_t *fst1 = h->status, *fst2 = nullptr;
+    int S1 = 1;
+    if (h->cfg.solver == PDPLQR_SOLVER_PARALLEL) parallel_status_view(h, &fst1, &S1, &fst2);
+    if ((rc = launch_polish_accept(sh.batch, s->conv, s->pmeas, fst1, S1, fst2, s->pstat, S))) return rc;
+    return launch_polish_write(sh, s->pstat, s->pw, s->py, s->pv, s->lb, s->ub, s->w, s->y, s->z, S);
+}
 
 }  // namespace pdplqr
 
@@ -792,8 +897,11 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
         q.active = s->active;
         q.rscale = s->rscale;
     }
+    const bool polish = h->polish_on != 0;
+    if (polish && (rc = polish_alloc(h))) return rc;
     s->solved_once = true;
     s->detect_last = detect;
+    s->polish_last = polish;
 
     const bool kkt = h->cfg.solver == PDPLQR_SOLVER_KKT;
     AdmmArgs a = admm_args(h, st);
@@ -892,8 +1000,20 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
         }
         if (last) break;
     }
+    // polish (off: nothing launches or copies anything new).  No rows: the LQ
+    // solve is the optimum, nothing is attempted.
+    if (polish) {
+        if (Y > 0) {
+            if ((rc = admm_polish(h, S))) return rc;
+        } else {
+            PDPLQR_HIP_TRY(hipMemsetAsync(s->pstat, 0, B * sizeof(int32_t), S));
+            PDPLQR_HIP_TRY(hipMemsetAsync(s->pnact, 0, B * sizeof(int32_t), S));
+            PDPLQR_HIP_TRY(hipMemsetAsync(s->pmeas, 0, B * 8 * sizeof(double), S));
+        }
+    }
     // fused iterations leave h~/g of the NEXT x-update in the workspace; the
-    // protocol state is "updated and factored" either way
+    // protocol state is "updated and factored" either way (after a polish: for
+    // the polishing system, a following forward returns the last polish iterate)
     if ((rc = admm_end(h, S, mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ws, ys, zs)))
         return rc;
     if (mem != PDPLQR_MEM_DEVICE) PDPLQR_HIP_TRY(hipStreamSynchronize(S));
@@ -1048,6 +1168,84 @@ int pdplqr_admm_check_certificates(pdplqr_handle h, const double *x0, const doub
     if (mem != PDPLQR_MEM_DEVICE) {
         PDPLQR_HIP_TRY(hipMemcpyAsync(measures, bm.p, B * 8 * sizeof(double), hipMemcpyDeviceToHost, S));
         PDPLQR_HIP_TRY(hipMemcpyAsync(verdict, bv.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, S));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    }
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_set_polish(pdplqr_handle h, int enable, double delta, int32_t refine_iter) {
+    if (!h) return PDPLQR_ERR_INVALID;
+    if (!enable) {
+        h->polish_on = 0;
+        return PDPLQR_OK;
+    }
+    if (!(delta > 0.0) || !(delta < 1.0e300) || refine_iter < 0) {  // (NaN fails the comparisons)
+        set_error("set_polish: delta must be a finite number > 0 and refine_iter >= 0");
+        return PDPLQR_ERR_INVALID;
+    }
+    if (const char *why = infeas_unsupported(h)) {  // the same limits: E on one device, hard dynamics, n + m <= 64
+        set_error(std::string("polish / ") + why);
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
+    h->polish_on = 1;
+    h->polish_delta = delta;
+    h->polish_refine = refine_iter;
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_polish_info(pdplqr_handle h, int32_t *status, int32_t *n_active, double *measures) {
+    if (!h) return PDPLQR_ERR_INVALID;
+    if (!h->admm || !h->admm->solved_once || !h->admm->polish_last) {
+        set_error("admm_polish_info: the last admm_solve did not run with polish on");
+        return PDPLQR_ERR_STATE;
+    }
+    if (int brc = bind_device(h)) return brc;
+    PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
+    AdmmState *s = h->admm;
+    const size_t B = (size_t)h->sh.batch;
+    if (status) PDPLQR_HIP_TRY(hipMemcpy(status, s->pstat, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (n_active) PDPLQR_HIP_TRY(hipMemcpy(n_active, s->pnact, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (measures) PDPLQR_HIP_TRY(hipMemcpy(measures, s->pmeas, B * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_kkt_residuals(pdplqr_handle h, const double *x0, const double *lb, const double *ub,
+                              const double *ws, const double *ys, double *measures, int mem) {
+    if (!h || !measures) return PDPLQR_ERR_INVALID;
+    if (const char *why = infeas_unsupported(h)) {
+        set_error(std::string("kkt_residuals / ") + why);
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
+    if (!h->model_set) {
+        set_error("admm_kkt_residuals before set_model");
+        return PDPLQR_ERR_STATE;
+    }
+    const Shape &sh = h->sh;
+    if (!x0 || !ws || (sh.ny > 0 && (!lb || !ub || !ys))) {
+        set_error("admm_kkt_residuals: null x0 / ws / lb / ub / ys");
+        return PDPLQR_ERR_INVALID;
+    }
+    if (int brc = bind_device(h)) return brc;
+    hipStream_t S = h->stream;
+    const size_t B = (size_t)sh.batch, W = B * sh.perh, Y = B * sh.ny;
+    int rc;
+    CallBuf<double> bx, bl, bu, by, bw, bm;
+    if ((rc = bm.in(nullptr, B * 4, mem, S))) return rc;
+    if (mem == PDPLQR_MEM_DEVICE) bm.p = measures;
+    if ((rc = bx.in(x0, B * sh.n, mem, S)) || (rc = bw.in(ws, W, mem, S))) return rc;
+    if (Y > 0 && ((rc = bl.in(lb, Y, mem, S)) || (rc = bu.in(ub, Y, mem, S)) || (rc = by.in(ys, Y, mem, S)))) return rc;
+    KktArgs q{};
+    kkt_model_args(h, q);
+    q.x0 = bx.p;
+    q.lb = bl.p;
+    q.ub = bu.p;
+    q.w = bw.p;
+    q.y = by.p;
+    q.meas = bm.p;
+    q.mstride = 4;
+    if ((rc = launch_kkt_residual(q, S))) return rc;
+    if (mem != PDPLQR_MEM_DEVICE) {
+        PDPLQR_HIP_TRY(hipMemcpyAsync(measures, bm.p, B * 4 * sizeof(double), hipMemcpyDeviceToHost, S));
         PDPLQR_HIP_TRY(hipStreamSynchronize(S));
     }
     return PDPLQR_OK;

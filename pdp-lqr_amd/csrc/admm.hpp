@@ -75,6 +75,36 @@ int launch_infeas_snapshot(const Shape &sh, const int32_t *done, const double *y
 int launch_infeas_delta(long long total, long long per, const int32_t *status, const double *cur, const double *prev,
                         double *out, hipStream_t st);
 
+// The polish and the KKT measures (kernels_polish.hip).
+// measures of (w, y) into meas[b * mstride + 0..3]: row residual, dynamics
+// residual, reduced gradient, objective
+struct KktArgs {
+    Shape sh;
+    const double *E, *c, *H, *hv, *D, *x0, *lb, *ub, *w, *y;
+    const int32_t *d_off, *y_off;
+    int uni, max_nc;
+    double *meas;
+    int mstride;
+};
+struct PolishArgs {
+    Shape sh;
+    const double *D, *lb, *ub;
+    const double *y, *z;           // the ADMM iterate (classify)
+    const int32_t *d_off, *y_off;
+    int uni, max_nc;
+    double delta;
+    double *rho_p, *irho_p, *bt;   // [b][ny] the polishing x-update's rho, inv_rho and row targets
+    double *wp, *yp, *vp;          // the polish iterate (w, y) and v = D w
+    int32_t *nact;                 // [b] rows guessed active
+};
+int launch_polish_classify(const PolishArgs &a, hipStream_t st);
+int launch_polish_ystep(const PolishArgs &a, hipStream_t st);
+int launch_kkt_residual(const KktArgs &a, hipStream_t st);  // two launches: the recursion, the stage-local half
+int launch_polish_accept(int batch, const int32_t *conv, const double *meas, const int32_t *fst1, int S1,
+                         const int32_t *fst2, int32_t *pstat, hipStream_t st);
+int launch_polish_write(const Shape &sh, const int32_t *pstat, const double *wp, const double *yp, const double *vp,
+                        const double *lb, const double *ub, double *w, double *y, double *z, hipStream_t st);
+
 // Fused ADMM update + backward_without_factorization (kernels_nofact.hip):
 // PDPLQR_ERR_UNSUPPORTED when the shape / constraint layout is not covered.
 int launch_nofact_admm(const RiccatiArgs &r, const AdmmArgs &a, bool check, hipStream_t st);

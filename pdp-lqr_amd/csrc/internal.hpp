@@ -182,6 +182,10 @@ struct pdplqr_handle_s {
     // pdplqr_admm_set_infeasibility_detection (admm.hip, kernels_infeas.hip)
     int infeas_on = 0;
     double eps_prim_inf = 1e-4, eps_dual_inf = 1e-4;
+    // pdplqr_admm_set_polish (admm.hip, kernels_polish.hip)
+    int polish_on = 0;
+    double polish_delta = 1e-6;
+    int polish_refine = 3;
     int shard_last = 1;  // last shard_backward's is_last_shard
     pdplqr::MultiDev *md = nullptr;  // num_devices > 1 (multidev.hip): the slices' handles
     // replayable launch sequences of backward / backward_without_factorization /

@@ -247,6 +247,8 @@ int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact = true);
 int parallel_forward(pdplqr_handle h, const double *x0, double *ws, const double *left, const double *right,
                      int last_is_terminal, long long rstride = 0);
 int parallel_status(pdplqr_handle h, int32_t *flags);  // per-problem status (host)
+// the device flags parallel_status reads: seg_status [b][S], flag [b]
+void parallel_status_view(pdplqr_handle h, const int32_t **seg_status, int *S, const int32_t **flag);
 
 // The device segments of one problem: every reference segment (num_segments,
 // load_balancing: lqr_solver_parallel.hpp:70-81) cut into pieces of at most

@@ -354,6 +354,12 @@ int parallel_status(pdplqr_handle h, int32_t *flags) {
     return PDPLQR_OK;
 }
 
+void parallel_status_view(pdplqr_handle h, const int32_t **seg_status, int *S, const int32_t **flag) {
+    *seg_status = h->par->seg_status;
+    *S = h->par->S;
+    *flag = h->par->flag;
+}
+
 // the rank suffix scan's ping-pong and the rank maps of a fold over R ranks
 static int rank_fold_alloc(pdplqr_handle h, int R) {
     ParallelState *ps = h->par;

@@ -25,6 +25,10 @@ PDPLQR_ADMM_UNSOLVED = 0
 PDPLQR_ADMM_SOLVED = 1
 PDPLQR_ADMM_PRIMAL_INFEASIBLE = 2
 PDPLQR_ADMM_DUAL_INFEASIBLE = 3
+# pdplqr_admm_polish_info
+PDPLQR_POLISH_NOT_ATTEMPTED = 0
+PDPLQR_POLISH_ACCEPTED = 1
+PDPLQR_POLISH_REJECTED = 2
 
 ERRORS = {-1: "INVALID", -2: "HIP", -3: "ALLOC", -4: "STATE", -5: "UNSUPPORTED", -6: "NUMERIC"}
 
@@ -41,6 +45,7 @@ EXPORTS = [
     "pdplqr_adjoint", "pdplqr_adjoint_rows",
     "pdplqr_admm_set_infeasibility_detection", "pdplqr_admm_status", "pdplqr_admm_certificate",
     "pdplqr_admm_check_certificates",
+    "pdplqr_admm_set_polish", "pdplqr_admm_polish_info", "pdplqr_admm_kkt_residuals",
 ]
 
 
@@ -124,6 +129,10 @@ def lib() -> C.CDLL:
         L.pdplqr_admm_status.argtypes = [vp, ip]
         L.pdplqr_admm_certificate.argtypes = [vp, dp, dp, C.c_int]
         L.pdplqr_admm_check_certificates.argtypes = [vp, dp, dp, dp, dp, dp, C.c_double, C.c_double, dp, vp, C.c_int]
+    if hasattr(L, "pdplqr_admm_set_polish"):  # (absent from older A/B variants)
+        L.pdplqr_admm_set_polish.argtypes = [vp, C.c_int, C.c_double, i32]
+        L.pdplqr_admm_polish_info.argtypes = [vp, ip, ip, dp]
+        L.pdplqr_admm_kkt_residuals.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_adjoint"):  # (absent from older A/B variants)
         L.pdplqr_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_adjoint_rows"):  # (absent from older A/B variants)

@@ -215,12 +215,21 @@ class BoxLQRLayer:
     (``admm_info["status"]``: 2 = no feasible point, 3 = cost unbounded below);
     ``backward`` then raises ``RuntimeError`` naming the first such problem and
     its kind, before the "did not converge" error and whatever
-    ``allow_unconverged`` says."""
+    ``allow_unconverged`` says.
+
+    ``polish``: polish the solve (``pdplqr_admm_set_polish``): a problem whose
+    polished point passes OSQP's acceptance rule returns the optimum on its
+    active set instead of the ``eps``-accurate iterate
+    (``admm_info["polish_status"]``: 1 accepted, 2 rejected), so a loose
+    ``eps`` gives what thousands of iterations at a tight one gave.  The
+    explicit x-update the backward pass differentiates through then runs at
+    the polished ``(w, y, z)``, which is a fixed point of the ADMM step."""
 
     def __init__(self, n: int, m: int, N: int, batch: int, ncs, rho, sigma: float = 1e-6, alpha: float = 1.6,
                  eps: float = 1e-6, max_iter: int = 4000, adj_tol: float = 1e-8, adj_max_iter: int = 4000,
                  check_every: int = 25, allow_unconverged: bool = False, device: int = 0,
-                 detect_infeasible: bool = False, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
+                 detect_infeasible: bool = False, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4,
+                 polish: bool = False, polish_delta: float = 1e-6, polish_refine_iter: int = 3):
         from .solvers import admm_settings
 
         self.n, self.m, self.N, self.batch = int(n), int(m), int(N), int(batch)
@@ -246,6 +255,9 @@ class BoxLQRLayer:
         self._settings = admm_settings(sigma, alpha, max_iter, check_every, eps, 0.0, False)
         if self.detect_infeasible:
             self._hd.set_infeasibility_detection(True, eps_prim_inf, eps_dual_inf)
+        self.polish = bool(polish)
+        if self.polish:
+            self._hd.set_polish(True, polish_delta, polish_refine_iter)
         self._gen = 0
         self.admm_info = None
         self.adjoint_iterations = 0

@@ -126,6 +126,7 @@ class _Handle:
         self.nx, self.nu, self.N, self.batch = int(nx), int(nu), int(N), int(batch)
         self.ncs = self._ncs if self._ncs is not None else np.zeros(N + 1, dtype=np.int32)
         self.ny = int(np.sum(self.ncs))
+        self._polish = self._polish_ran = False  # set_polish's state; the last admm_solve ran with it on
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
@@ -263,6 +264,7 @@ class _Handle:
         mem = _mem_of(*ps)
         cur = self._enter(x0, lb, ub, rho, ws, ys, zs)
         check(lib().pdplqr_admm_solve(self.h, C.byref(settings), *[p[0] for p in ps], mem))
+        self._polish_ran = self._polish
         self._leave(cur)
 
     def admm_info(self):
@@ -275,8 +277,52 @@ class _Handle:
         n = check(lib().pdplqr_admm_info(self.h, it.ctypes.data_as(i32), cv.ctypes.data_as(i32),
                                          C.c_void_p(rp.ctypes.data), C.c_void_p(rd.ctypes.data),
                                          C.c_void_p(rho.ctypes.data)))
-        return {"iterations": int(n), "iters": it, "converged": cv.astype(bool), "prim_res": rp, "dual_res": rd,
+        info = {"iterations": int(n), "iters": it, "converged": cv.astype(bool), "prim_res": rp, "dual_res": rd,
                 "rho": rho[:, :self.ny], "status": self.admm_status()}
+        if self._polish_ran:
+            info["polish_status"] = self.polish_info()["status"]
+        return info
+
+    def set_polish(self, enable: bool, delta: float = 1e-6, refine_iter: int = 3):
+        """Switch the polish of ``admm_solve`` on or off (include/pdplqr.h:
+        pdplqr_admm_set_polish; OSQP's defaults).  With it on, a problem that
+        ended SOLVED gets the solution of the equality-constrained problem on its
+        guessed active rows when that passes OSQP's acceptance rule."""
+        check(lib().pdplqr_admm_set_polish(self.h, int(bool(enable)), float(delta), int(refine_iter)))
+        self._polish = bool(enable)
+
+    def polish_info(self):
+        """The polish of the last admm_solve: ``status`` (0 not attempted, 1
+        accepted, 2 rejected), ``n_active`` (rows guessed active) and ``measures``
+        [batch][8]: the KKT measures of the ADMM iterate, then of the polished pair."""
+        st = np.zeros(self.batch, dtype=np.int32)
+        na = np.zeros(self.batch, dtype=np.int32)
+        ms = np.zeros((self.batch, 8))
+        i32 = C.POINTER(C.c_int32)
+        check(lib().pdplqr_admm_polish_info(self.h, st.ctypes.data_as(i32), na.ctypes.data_as(i32),
+                                            C.c_void_p(ms.ctypes.data)))
+        return {"status": st, "n_active": na, "measures": ms}
+
+    def kkt_residuals(self, x0, lb, ub, ws, ys):
+        """The KKT measures of any ``(ws, ys)`` (pdplqr_admm_kkt_residuals; needs
+        only set_model).  Host (numpy) or device (torch) inputs; returns
+        ``measures [batch][4]`` in the same memory: row residual, dynamics
+        residual, reduced gradient, objective."""
+        objs = [x0, lb, ub, ws, ys]
+        ps = [_ptr(o, nm) for o, nm in zip(objs, ("x0", "lb", "ub", "ws", "ys"))]
+        mem = _mem_of(*ps)
+        if mem == _lib.PDPLQR_MEM_DEVICE:
+            import torch
+
+            meas = torch.zeros(self.batch, 4, dtype=torch.float64, device=ws.device)
+            pm = C.c_void_p(meas.data_ptr())
+        else:
+            meas = np.zeros((self.batch, 4))
+            pm = C.c_void_p(meas.ctypes.data)
+        cur = self._enter(*objs, meas)
+        check(lib().pdplqr_admm_kkt_residuals(self.h, *[p[0] for p in ps], pm, mem))
+        self._leave(cur)
+        return meas
 
     def set_infeasibility_detection(self, enable: bool, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
         """Switch OSQP's infeasibility certificates of ``admm_solve`` on or off
@@ -578,6 +624,17 @@ class BatchedLQRSolver:
 
     def admm_info(self):
         return self._hd.admm_info()
+
+    def set_polish(self, enable: bool, delta: float = 1e-6, refine_iter: int = 3):
+        """Polish the solutions of the following ``admm_solve`` calls (off by
+        default; ``admm_info()["polish_status"]``, ``polish_info()``)."""
+        self._hd.set_polish(enable, delta, refine_iter)
+
+    def polish_info(self):
+        return self._hd.polish_info()
+
+    def kkt_residuals(self, x0, lb, ub, ws, ys):
+        return self._hd.kkt_residuals(x0, lb, ub, ws, ys)
 
     def value_function(self, b, k):
         return self._hd.value_function(b, k)
