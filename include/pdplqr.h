@@ -452,6 +452,57 @@ int pdplqr_admm_polish_info(pdplqr_handle h, int32_t *status, int32_t *n_active,
 int pdplqr_admm_kkt_residuals(pdplqr_handle h, const double *x0, const double *lb, const double *ub,
                               const double *ws, const double *ys, double *measures, int mem);
 
+/* ---------------------------------------------------------------------- */
+/* Gradients of the box-constrained optimum of the last admm_solve (new;    */
+/* DESIGN.md 5.9).  The polish left a guessed active set (rows D_a, targets */
+/* b: lb on the lower-active rows, ub on the upper-active ones) and a       */
+/* handle that factors the polishing system H + delta I + D_a^T D_a / delta. */
+/* The adjoint of the equality-constrained KKT solve on that set is one     */
+/* more solve with the same symmetric matrix, so the polish's iterative     */
+/* refinement serves it with another right-hand side.  On the handle's      */
+/* stream, with no host wait:                                                */
+/*   1. the polishing x-update at the returned (w, y) is run again          */
+/*      (update_problem_data, backward, forward): factor, lp and its        */
+/*      solution w~ belong together whatever protocol calls ran in between; */
+/*   2. g~ = gws + D^T gvs;                                                  */
+/*   3. v = 0, eta = 0; refine_iter + 1 times: v <- the adjoint solve on    */
+/*      the cached factor with h~ := g~ - delta v + D_a^T eta, c := 0,      */
+/*      x0 := 0 (pdplqr_adjoint's); eta <- eta + (D_a v) / delta;           */
+/*   4. gE, gc, gH, gh, gx by pdplqr_adjoint's formulas on (w~, v), and     */
+/*      with y_a = y on the active rows, 0 elsewhere:                        */
+/*        gD  = y_a,k v_k^T + (eta_k + gvs_k) w~_k^T   (D's layout)         */
+/*        glb = -eta on the lower-active rows, gub = -eta on the upper-     */
+/*        active rows, 0 elsewhere.  A row's side is the polish             */
+/*        classification's: a row with lb == ub is lower-active, its whole  */
+/*        gradient goes to glb.                                              */
+/* gws = dl/dws [batch][N*s+n]; gvs = dl/d(D ws) [batch][ny] (NULL = 0);     */
+/* gE, gc, gH, gh, gx, gD in the boundary layouts of pdplqr_adjoint_rows;    */
+/* glb, gub [batch][ny].  Any output may be NULL: its work and stores are   */
+/* skipped.  All non-NULL pointers live in `mem`.  delta and refine_iter    */
+/* are the handle's (pdplqr_admm_set_polish).  Everything                   */
+/* pdplqr_adjoint_rows requires (SERIAL, keep_factors = 1, one device,      */
+/* nx + nu <= 64, every stage's rows within the rows kernel's LDS tile),    */
+/* at least one constraint row, and the last pdplqr_admm_solve ran with     */
+/* polish on; PDPLQR_ERR_UNSUPPORTED / PDPLQR_ERR_STATE otherwise.  A       */
+/* refused call writes nothing.  The call reads only what that solve left   */
+/* (w, y, x0, lb, ub, the classification).  Afterwards the handle is        */
+/* "updated and factored" for the polishing system at the solution: a       */
+/* following pdplqr_forward returns w~; admm_info, admm_status, polish_info */
+/* and the solve's w, y, z are untouched.                                    */
+/* ---------------------------------------------------------------------- */
+#define PDPLQR_ADMM_ADJOINT_EXACT 1  /* the polish was accepted: the optimum's gradient if the guess was right */
+#define PDPLQR_ADMM_ADJOINT_APPROX 2 /* polish rejected or not SOLVED: the guessed set at the ADMM iterate     */
+#define PDPLQR_ADMM_ADJOINT_FAILED 3 /* the factorisation of step 1 failed: this problem's outputs are unspecified */
+
+int pdplqr_admm_adjoint(pdplqr_handle h, const double *gws, const double *gvs, double *gE, double *gc, double *gH,
+                        double *gh, double *gx, double *gD, double *glb, double *gub, int mem);
+
+/* The last pdplqr_admm_adjoint, host arrays, either may be NULL: status     */
+/* [batch] (PDPLQR_ADMM_ADJOINT_*); resid [batch][2]: max|D_a v| / max|v|    */
+/* after the last step, and max|v_new - v_old| / max|v_new| of the last step. */
+/* PDPLQR_ERR_STATE before any pdplqr_admm_adjoint.                           */
+int pdplqr_admm_adjoint_info(pdplqr_handle h, int32_t *status, double *resid);
+
 /* Device info helpers (for hosts that do not link HIP). */
 int pdplqr_device_count(int32_t *count);
 

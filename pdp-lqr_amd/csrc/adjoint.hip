@@ -15,6 +15,7 @@
 #include <string>
 
 #include "adjoint.hpp"
+#include "admm.hpp"
 #include "solvers.hpp"
 
 namespace pdplqr {
@@ -28,6 +29,12 @@ struct AdjointState {
     // host outputs' staging (gE, gc, gH, gh, gx, gD, gg, grho)
     double *out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double *rho = nullptr, *gvs = nullptr;  // host rho / gvs staging (pdplqr_adjoint_rows)
+    // pdplqr_admm_adjoint (allocated by its first call)
+    double *gt = nullptr, *eta = nullptr;   // g~ = gws + D^T gvs; the multiplier of the active rows
+    double *wt = nullptr, *v2 = nullptr;    // w~ of the x-update at the solution; the other adjoint iterate
+    double *resid = nullptr;                // [b][2]
+    int32_t *stat = nullptr;                // [b] PDPLQR_ADMM_ADJOINT_*
+    bool as_ran = false;                    // an admm_adjoint got as far as its launches
 };
 
 void adjoint_release(pdplqr_handle h) {
@@ -84,6 +91,18 @@ static AdjointArgs adjoint_args(pdplqr_handle h, const double *ws, double *gE, d
     g.gh = gh;
     g.gx = gx;
     return g;
+}
+
+// the adjoint solve on the cached factor: h~ := rhs, c := 0, x0 := 0, lp into the
+// scratch's own lpa; the caller saves and restores the record's lu'
+static int adjoint_solve(pdplqr_handle h, double *rhs, double *v) {
+    AdjointState *s = h->adj;
+    RiccatiArgs a = riccati_args(h);  // (xl_ws: null on these handles, n + m <= 64)
+    a.c = s->zc;
+    a.hw = rhs;
+    a.lpc = s->lpa;
+    const int rc = launch_riccati_backward_nofact(a, h->stream);
+    return rc ? rc : launch_riccati_forward(h->sh, h->E, s->zc, h->KD, s->zx0, v, h->stream);
 }
 
 static int fail(int code, const char *msg) {
@@ -149,12 +168,7 @@ static int adjoint_run(pdplqr_handle h, const char *what, const double *ws, cons
 
     // v: backward_without_factorization + forward of (E, H~) with h~ := g, c := 0, x0 := 0
     if ((rc = launch_adjoint_lu(sh, h->KD, s->lus, false, st))) return rc;
-    RiccatiArgs a = riccati_args(h);  // (xl_ws: null on these handles, n + m <= 64)
-    a.c = s->zc;
-    a.hw = s->rhs;
-    a.lpc = s->lpa;
-    rc = launch_riccati_backward_nofact(a, st);
-    if (!rc) rc = launch_riccati_forward(sh, h->E, s->zc, h->KD, s->zx0, s->v, st);
+    rc = adjoint_solve(h, s->rhs, s->v);
     // the record's lu' goes back whatever the launches returned
     const int rc2 = launch_adjoint_lu(sh, h->KD, s->lus, true, st);
     if (rc || rc2) return rc ? rc : rc2;
@@ -238,4 +252,214 @@ extern "C" int pdplqr_debug_adjoint_grad(pdplqr_handle h, const double *ws, doub
     if (!h || !ws || !h->adj || !h->Lc || !h->lpc) return fail(PDPLQR_ERR_STATE, "debug_adjoint_grad before adjoint");
     if (int brc = bind_device(h)) return brc;
     return launch_adjoint_grad(adjoint_args(h, ws, gE, gc, gH, gh, gx), h->stream);
+}
+
+// The gradient of the box-constrained optimum of the last admm_solve on the
+// active set its polish guessed (include/pdplqr.h):
+// the polishing x-update at the returned point, then refine_iter + 1 adjoint
+// solves on its factor with k_asadj_step between them, the gradient pass of
+// pdplqr_adjoint and k_asadj_rows.  Nothing here waits for the device (device
+// buffers).
+extern "C" int pdplqr_admm_adjoint(pdplqr_handle h, const double *gws, const double *gvs, double *gE, double *gc,
+                                   double *gH, double *gh, double *gx, double *gD, double *glb, double *gub,
+                                   int mem) {
+    if (!h) return fail(PDPLQR_ERR_INVALID, "admm_adjoint: null handle");
+    if (!gws) return fail(PDPLQR_ERR_INVALID, "admm_adjoint: null gws");
+    if (h->md) return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint: multi-device handles are not supported");
+    if (h->cfg.solver != PDPLQR_SOLVER_SERIAL)
+        return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint needs a SERIAL handle (PARALLEL and KKT are not supported)");
+    const Shape &sh = h->sh;
+    if (sh.s > 64) return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint: n + m > 64 is not supported");
+    if (sh.ny == 0)
+        return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint: the handle has no constraint rows (use pdplqr_adjoint)");
+    if (!h->cfg.keep_factors || !h->Lc || !h->lpc)
+        return fail(PDPLQR_ERR_STATE, "admm_adjoint requires keep_factors = 1");
+    AdmmAdjointView V;
+    const int vrc = h->model_set ? admm_adjoint_view(h, V) : 1;
+    if (vrc == 1) return fail(PDPLQR_ERR_STATE, "admm_adjoint before admm_solve");
+    if (vrc) return fail(PDPLQR_ERR_STATE, "admm_adjoint: the last admm_solve did not run with polish on");
+    if (int brc = bind_device(h)) return brc;
+    AdjointRowsArgs plan;
+    if (!adjoint_rows_plan(sh, h->y_off_h.data(), h->d_off_h.data(), plan))
+        return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint: the constraint rows of one stage exceed the kernel's LDS tile");
+    int rc = adjoint_alloc(h);
+    if (rc) return rc;
+    AdjointState *s = h->adj;
+    const long long B = sh.batch;
+    if (!s->gt && ((rc = dev_alloc(h, &s->gt, B * sh.perh)) || (rc = dev_alloc(h, &s->eta, B * sh.ny)) ||
+                   (rc = dev_alloc(h, &s->wt, B * sh.perh)) || (rc = dev_alloc(h, &s->v2, B * sh.perh)) ||
+                   (rc = dev_alloc(h, &s->resid, 2 * B)) || (rc = dev_alloc(h, &s->stat, B)))) {
+        s->gt = nullptr;  // (what was allocated is freed with the handle)
+        return rc;
+    }
+    const bool dev = mem == PDPLQR_MEM_DEVICE;
+    hipStream_t st = h->stream;
+    const hipMemcpyKind in = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const double delta = h->polish_delta;
+    const int refine = h->polish_refine;
+
+    // g~ = gws (+ D^T gvs), in the scratch: the recursion never reads the caller's buffer
+    const double *dgvs = gvs;
+    if (!dev && gvs) {
+        if (!s->gvs && (rc = dev_alloc(h, &s->gvs, B * sh.ny))) return rc;
+        if ((rc = stage_in(h, gvs, s->gvs, B * sh.ny, mem, &dgvs))) return rc;
+    }
+    if (gvs && dev) {
+        if ((rc = launch_adjoint_rhs(sh, gws, dgvs, h->D, h->d_off, h->y_off, s->gt, st))) return rc;
+    } else {
+        PDPLQR_HIP_TRY(hipMemcpyAsync(s->gt, gws, (size_t)(B * sh.perh) * sizeof(double), in, st));
+        if (gvs && (rc = launch_adjoint_rhs(sh, s->gt, dgvs, h->D, h->d_off, h->y_off, s->gt, st))) return rc;
+    }
+    // outputs: the caller's device pointers, or staging allocated on first use
+    // (glb, gub share the staging of pdplqr_adjoint_rows's gg, grho: [b][ny] each)
+    double *const user[8] = {gE, gc, gH, gh, gx, gD, glb, gub};
+    const long long cnt[8] = {B * sh.perE, B * sh.perc, B * sh.perH, B * sh.perh, B * sh.n,
+                              B * sh.ndD,  B * sh.ny,   B * sh.ny};
+    double *out[8];
+    for (int i = 0; i < 8; ++i) {
+        out[i] = cnt[i] > 0 ? user[i] : nullptr;
+        if (out[i] && !dev) {
+            if (!s->out[i] && (rc = dev_alloc(h, &s->out[i], cnt[i]))) return rc;
+            out[i] = s->out[i];
+        }
+    }
+
+    // 1. the polishing x-update at the returned point: factor, lp and w~ belong together
+    //    (y enters through g = b - inv_rho o y only, and inv_rho is 0 off the active rows)
+    if ((rc = solver_update(h, V.w, V.y, V.pb, V.pirho, delta))) return rc;
+    h->updated = true;
+    if ((rc = solver_backward(h, V.prho))) return rc;
+    h->factored = true;
+    if ((rc = solver_forward(h, V.x0, s->wt))) return rc;
+    s->as_ran = true;
+
+    // 3. v^0 = 0, eta^0 = 0: the first right-hand side is g~ itself; iterate j + 1 goes to vb[(j + 1) & 1]
+    PDPLQR_HIP_TRY(hipMemsetAsync(s->eta, 0, (size_t)(B * sh.ny) * sizeof(double), st));
+    double *const vb[2] = {s->v2, s->v};
+    AsadjStepArgs q{};
+    q.sh = sh;
+    q.D = h->D;
+    q.act = V.prho;
+    q.d_off = h->d_off;
+    q.y_off = h->y_off;
+    q.max_nc = h->max_nc;
+    q.delta = delta;
+    q.gt = s->gt;
+    q.eta = s->eta;
+    q.pstat = V.pstat;
+    q.fstat = h->status;
+    if ((rc = launch_adjoint_lu(sh, h->KD, s->lus, false, st))) return rc;
+    for (int j = 0; j <= refine && !rc; ++j) {
+        const bool last = j == refine;
+        q.v = vb[(j + 1) & 1];
+        q.vprev = j > 0 ? vb[j & 1] : nullptr;
+        q.rhs = last ? nullptr : s->rhs;
+        q.resid = last ? s->resid : nullptr;
+        q.stat = last ? s->stat : nullptr;
+        rc = adjoint_solve(h, j == 0 ? s->gt : s->rhs, vb[(j + 1) & 1]);
+        if (!rc) rc = launch_asadj_step(q, st);
+    }
+    // the record's lu' goes back whatever the launches returned
+    const int rc2 = launch_adjoint_lu(sh, h->KD, s->lus, true, st);
+    if (rc || rc2) return rc ? rc : rc2;
+    const double *v = vb[(refine + 1) & 1];
+
+    // 4. the gradients: pdplqr_adjoint's pass on (w~, v), then the rows
+    AdjointArgs g = adjoint_args(h, s->wt, out[0], out[1], out[2], out[3], out[4]);
+    g.v = v;
+    if ((rc = launch_adjoint_grad(g, st))) return rc;
+    if (out[5] || out[6] || out[7]) {
+        AsadjRowsArgs ra;
+        ra.sh = sh;
+        ra.ws = s->wt;
+        ra.v = v;
+        ra.y = V.y;
+        ra.eta = s->eta;
+        ra.gvs = dgvs;
+        ra.act = V.prho;
+        ra.bt = V.pb;
+        ra.lb = V.lb;
+        ra.d_off = h->d_off;
+        ra.y_off = h->y_off;
+        ra.gD = out[5];
+        ra.glb = out[6];
+        ra.gub = out[7];
+        ra.ts = plan.ts;
+        ra.max_rows = plan.max_rows;
+        if ((rc = launch_asadj_rows(ra, h->y_off_h.data(), h->d_off_h.data(), st))) return rc;
+    }
+
+    if (!dev) {
+        for (int i = 0; i < 8; ++i)
+            if (out[i])
+                PDPLQR_HIP_TRY(hipMemcpyAsync(user[i], out[i], (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, st));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(st));
+    }
+    h->host_staged = false;
+    return PDPLQR_OK;
+}
+
+extern "C" int pdplqr_admm_adjoint_info(pdplqr_handle h, int32_t *status, double *resid) {
+    if (!h) return fail(PDPLQR_ERR_INVALID, "admm_adjoint_info: null handle");
+    if (!h->adj || !h->adj->as_ran) return fail(PDPLQR_ERR_STATE, "admm_adjoint_info before admm_adjoint");
+    if (int brc = bind_device(h)) return brc;
+    PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t B = (size_t)h->sh.batch;
+    if (status) PDPLQR_HIP_TRY(hipMemcpy(status, h->adj->stat, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (resid) PDPLQR_HIP_TRY(hipMemcpy(resid, h->adj->resid, 2 * B * sizeof(double), hipMemcpyDeviceToHost));
+    return PDPLQR_OK;
+}
+
+// Internal diagnostics (not part of include/pdplqr.h; scripts/admm_adjoint_bench.py):
+// the two kernels of pdplqr_admm_adjoint alone, on what its last call left in
+// the scratch.  Device pointers.  The step is a middle one (eta stepped, rhs
+// written); eta is scratch: the next admm_adjoint starts it from zero.
+extern "C" int pdplqr_debug_asadj_step(pdplqr_handle h) {
+    AdmmAdjointView V;
+    if (!h || !h->adj || !h->adj->as_ran || admm_adjoint_view(h, V))
+        return fail(PDPLQR_ERR_STATE, "debug_asadj_step before admm_adjoint");
+    if (int brc = bind_device(h)) return brc;
+    AdjointState *s = h->adj;
+    AsadjStepArgs q{};
+    q.sh = h->sh;
+    q.D = h->D;
+    q.act = V.prho;
+    q.d_off = h->d_off;
+    q.y_off = h->y_off;
+    q.max_nc = h->max_nc;
+    q.delta = h->polish_delta;
+    q.v = s->v;
+    q.gt = s->gt;
+    q.eta = s->eta;
+    q.rhs = s->rhs;
+    return launch_asadj_step(q, h->stream);
+}
+
+extern "C" int pdplqr_debug_asadj_rows(pdplqr_handle h, double *gD, double *glb, double *gub) {
+    AdmmAdjointView V;
+    if (!h || !h->adj || !h->adj->as_ran || admm_adjoint_view(h, V))
+        return fail(PDPLQR_ERR_STATE, "debug_asadj_rows before admm_adjoint");
+    if (int brc = bind_device(h)) return brc;
+    AdjointRowsArgs plan;
+    if (!adjoint_rows_plan(h->sh, h->y_off_h.data(), h->d_off_h.data(), plan))
+        return fail(PDPLQR_ERR_UNSUPPORTED, "debug_asadj_rows: rows exceed the LDS tile");
+    AdjointState *s = h->adj;
+    AsadjRowsArgs ra;
+    ra.sh = h->sh;
+    ra.ws = s->wt;
+    ra.v = s->v;
+    ra.y = V.y;
+    ra.eta = s->eta;
+    ra.gvs = nullptr;
+    ra.act = V.prho;
+    ra.bt = V.pb;
+    ra.lb = V.lb;
+    ra.d_off = h->d_off;
+    ra.y_off = h->y_off;
+    ra.gD = gD;
+    ra.glb = glb;
+    ra.gub = gub;
+    ra.ts = plan.ts;
+    ra.max_rows = plan.max_rows;
+    return launch_asadj_rows(ra, h->y_off_h.data(), h->d_off_h.data(), h->stream);
 }

@@ -39,4 +39,36 @@ int launch_adjoint_rows(const AdjointRowsArgs &a, const int32_t *y_off_h, const 
 int launch_adjoint_rhs(const Shape &sh, const double *gws, const double *gvs, const double *D, const int32_t *d_off,
                        const int32_t *y_off, double *rhs, hipStream_t st);
 
+size_t adjoint_rows_lds_bytes(const Shape &sh, int ts, int max_rows);  // the rows kernels' tile
+
+// pdplqr_admm_adjoint: the refinement step and the row gradients (kernels_asadj.hip)
+struct AsadjStepArgs {
+    Shape sh;
+    const double *D, *act;         // act [b][ny]: != 0 on the active rows (the polish's rho)
+    const int32_t *d_off, *y_off;
+    int max_nc;
+    double delta;
+    const double *v, *gt;          // the new adjoint iterate and g~, [b][N*s + n]
+    double *eta;                   // [b][ny], stepped in place on the active rows
+    double *rhs;                   // out: g~ - delta v + D^T eta (NULL: not wanted, the last step)
+    // the last step (resid non-NULL): the measures and the status of every problem
+    const double *vprev;           // the iterate before (NULL: zero)
+    double *resid;                 // [b][2]
+    int32_t *stat;                 // [b] PDPLQR_ADMM_ADJOINT_*
+    const int32_t *pstat, *fstat;  // the polish outcome and the factorisation status
+};
+int launch_asadj_step(const AsadjStepArgs &a, hipStream_t st);
+
+struct AsadjRowsArgs {
+    Shape sh;
+    const double *ws, *v;                  // w~ and the adjoint solution [b][N*s + n]
+    const double *y, *eta, *gvs;           // [b][ny]; gvs NULL = zero
+    const double *act, *bt, *lb;           // the classification: active flag, target, lower bound
+    const int32_t *d_off, *y_off;
+    double *gD, *glb, *gub;                // outputs; NULL = not wanted
+    int ts = 0, max_rows = 0;              // adjoint_rows_plan's tile
+    int vecD = 0, vecY = 0;                // 16-byte stores allowed (set by the launcher)
+};
+int launch_asadj_rows(const AsadjRowsArgs &a, const int32_t *y_off_h, const int32_t *d_off_h, hipStream_t st);
+
 }  // namespace pdplqr

@@ -823,6 +823,21 @@ static int admm_polish(pdplqr_handle h, hipStream_t S) {
     return launch_polish_write(sh, s->pstat, s->pw, s->py, s->pv, s->lb, s->ub, s->w, s->y, s->z, S);
 }
 
+int admm_adjoint_view(pdplqr_handle h, AdmmAdjointView &v) {
+    const AdmmState *s = h->admm;
+    if (!s || !s->solved_once) return 1;
+    if (!s->polish_last || !s->prho) return 2;
+    v.w = s->w;
+    v.y = s->y;
+    v.x0 = s->x0;
+    v.lb = s->lb;
+    v.prho = s->prho;
+    v.pirho = s->pirho;
+    v.pb = s->pb;
+    v.pstat = s->pstat;
+    return 0;
+}
+
 }  // namespace pdplqr
 
 using namespace pdplqr;

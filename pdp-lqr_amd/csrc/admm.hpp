@@ -105,6 +105,16 @@ int launch_polish_accept(int batch, const int32_t *conv, const double *meas, con
 int launch_polish_write(const Shape &sh, const int32_t *pstat, const double *wp, const double *yp, const double *vp,
                         const double *lb, const double *ub, double *w, double *y, double *z, hipStream_t st);
 
+// What pdplqr_admm_adjoint (adjoint.hip) reads of the last admm_solve: the
+// returned point, the call's vectors and the polish classification.
+struct AdmmAdjointView {
+    const double *w, *y, *x0, *lb;
+    const double *prho, *pirho, *pb;  // 1/delta | 0, delta | 0 and the target of every row
+    const int32_t *pstat;             // [b] PDPLQR_POLISH_*
+};
+// 0: filled; 1: no admm_solve has run; 2: the last one ran without polish
+int admm_adjoint_view(pdplqr_handle h, AdmmAdjointView &v);
+
 // Fused ADMM update + backward_without_factorization (kernels_nofact.hip):
 // PDPLQR_ERR_UNSUPPORTED when the shape / constraint layout is not covered.
 int launch_nofact_admm(const RiccatiArgs &r, const AdmmArgs &a, bool check, hipStream_t st);

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void k_adjoint_rhs(Shape sh, const double *gws
     }
 }
 
-static size_t rows_lds_bytes(const Shape &sh, int ts, int max_rows) {
+size_t adjoint_rows_lds_bytes(const Shape &sh, int ts, int max_rows) {
     return sizeof(double) * (2ull * ts * sh.s + 4ull * max_rows) + sizeof(int) * 2ull * (ts + 1);
 }
 
@@ -158,7 +158,7 @@ static int rows_of_tile(const Shape &sh, const int32_t *y_off_h, int ts) {
 // one stage alone does not (about 1,270 rows on a stage at n + m = 6)
 bool adjoint_rows_plan(const Shape &sh, const int32_t *y_off_h, const int32_t *, AdjointRowsArgs &a) {
     int ts = 16;
-    auto bytes = [&](int t) { return rows_lds_bytes(sh, t, rows_of_tile(sh, y_off_h, t)); };
+    auto bytes = [&](int t) { return adjoint_rows_lds_bytes(sh, t, rows_of_tile(sh, y_off_h, t)); };
     while (ts > 1 && (bytes(ts) > 40 * 1024 || ts >= 2 * (sh.N + 1))) ts >>= 1;
     a.sh = sh;
     a.ts = ts;
@@ -166,7 +166,7 @@ bool adjoint_rows_plan(const Shape &sh, const int32_t *y_off_h, const int32_t *,
     // lanes per row of the two row products: as many as keep the fullest tile within one pass of the block
     a.lanes = 1;
     while (a.lanes < 16 && a.max_rows * a.lanes * 2 <= 256) a.lanes <<= 1;
-    return rows_lds_bytes(sh, ts, a.max_rows) <= 40 * 1024;
+    return adjoint_rows_lds_bytes(sh, ts, a.max_rows) <= 40 * 1024;
 }
 
 int launch_adjoint_rows(const AdjointRowsArgs &a0, const int32_t *y_off_h, const int32_t *d_off_h, hipStream_t st) {
@@ -187,7 +187,8 @@ int launch_adjoint_rows(const AdjointRowsArgs &a0, const int32_t *y_off_h, const
     }
     a.vecD = evD && al(a.gD);
     a.vecY = evY && al(a.gg) && al(a.grho);
-    hipLaunchKernelGGL(k_adjoint_rows, dim3((unsigned)blocks), dim3(256), rows_lds_bytes(sh, a.ts, a.max_rows), st, a);
+    const size_t lds = adjoint_rows_lds_bytes(sh, a.ts, a.max_rows);
+    hipLaunchKernelGGL(k_adjoint_rows, dim3((unsigned)blocks), dim3(256), lds, st, a);
     PDPLQR_HIP_TRY(hipGetLastError());
     return PDPLQR_OK;
 }

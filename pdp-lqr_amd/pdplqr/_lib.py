@@ -29,6 +29,10 @@ PDPLQR_ADMM_DUAL_INFEASIBLE = 3
 PDPLQR_POLISH_NOT_ATTEMPTED = 0
 PDPLQR_POLISH_ACCEPTED = 1
 PDPLQR_POLISH_REJECTED = 2
+# pdplqr_admm_adjoint_info
+PDPLQR_ADMM_ADJOINT_EXACT = 1
+PDPLQR_ADMM_ADJOINT_APPROX = 2
+PDPLQR_ADMM_ADJOINT_FAILED = 3
 
 ERRORS = {-1: "INVALID", -2: "HIP", -3: "ALLOC", -4: "STATE", -5: "UNSUPPORTED", -6: "NUMERIC"}
 
@@ -46,6 +50,7 @@ EXPORTS = [
     "pdplqr_admm_set_infeasibility_detection", "pdplqr_admm_status", "pdplqr_admm_certificate",
     "pdplqr_admm_check_certificates",
     "pdplqr_admm_set_polish", "pdplqr_admm_polish_info", "pdplqr_admm_kkt_residuals",
+    "pdplqr_admm_adjoint", "pdplqr_admm_adjoint_info",
 ]
 
 
@@ -137,6 +142,9 @@ def lib() -> C.CDLL:
         L.pdplqr_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_adjoint_rows"):  # (absent from older A/B variants)
         L.pdplqr_adjoint_rows.argtypes = [vp] + [dp] * 12 + [C.c_int]
+    if hasattr(L, "pdplqr_admm_adjoint"):  # (absent from older A/B variants)
+        L.pdplqr_admm_adjoint.argtypes = [vp] + [dp] * 10 + [C.c_int]
+        L.pdplqr_admm_adjoint_info.argtypes = [vp, ip, dp]
     if hasattr(L, "pdplqr_multidev_plan"):  # (absent from pre-round-4 A/B variants)
         L.pdplqr_multidev_plan.argtypes = [i32, i32, ip, i32, i32, C.POINTER(C.c_int64)]
     for nm in EXPORTS:

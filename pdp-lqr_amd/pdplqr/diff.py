@@ -104,12 +104,15 @@ class _BoxLQRSolve(torch.autograd.Function):
         ws, ys, zs = new(layer._per[3]), new(layer.ny), new(layer.ny)  # the zero start
         hd.admm_solve(ins[4], ins[6], ins[7], rho, ws, ys, zs, layer._settings)
         layer.admm_info = hd.admm_info()
-        # one protocol x-update at the returned (w*, y*, z*): the handle's factor, g and
-        # lp now belong to the fixed point, whatever path admm_solve's last iteration took
-        hd.update_problem_data(ws, ys, zs, layer._irho, layer.sigma)
-        hd.backward(rho)
-        wt = torch.empty_like(ws)
-        hd.forward(ins[4], wt)
+        if layer.backward_mode == "active_set":
+            wt = ws  # (pdplqr_admm_adjoint factors for itself, at the point the solve left in the handle)
+        else:
+            # one protocol x-update at the returned (w*, y*, z*): the handle's factor, g and
+            # lp now belong to the fixed point, whatever path admm_solve's last iteration took
+            hd.update_problem_data(ws, ys, zs, layer._irho, layer.sigma)
+            hd.backward(rho)
+            wt = torch.empty_like(ws)
+            hd.forward(ins[4], wt)
         layer._gen += 1  # the handle now holds THIS call's factorization
         ctx.layer, ctx.gen = layer, layer._gen
         ctx.converged = bool(layer.admm_info["converged"].all())
@@ -139,6 +142,8 @@ class _BoxLQRSolve(torch.autograd.Function):
             raise RuntimeError(
                 f"BoxLQRLayer: problem {ctx.infeasible[0]} of the batch is {ctx.infeasible[1]} (layer.admm_info"
                 '["status"]); there is no optimum to differentiate.')
+        if layer.backward_mode == "active_set":  # (its own status decides, per problem)
+            return _BoxLQRSolve._backward_active_set(ctx, layer, gws.contiguous())
         if not ctx.converged and not layer.allow_unconverged:
             raise RuntimeError(
                 "BoxLQRLayer: the ADMM solve being differentiated did not converge for every problem of the batch "
@@ -185,6 +190,26 @@ class _BoxLQRSolve(torch.autograd.Function):
         outs.append(q * at_ub if need[7] else None)
         return (None,) + tuple(o.view(shp) if o is not None else None for o, shp in zip(outs, ctx.shapes))
 
+    @staticmethod
+    def _backward_active_set(ctx, layer, gws):
+        """One pdplqr_admm_adjoint call, asking only for what autograd needs."""
+        hd = layer._hd
+        outs = [torch.empty(layer.batch, cnt, dtype=torch.float64, device=layer._dev) if nd else None
+                for cnt, nd in zip(layer._per, ctx.needs_input_grad[1:])]
+        hd.admm_adjoint(gws.contiguous(), None, *outs)
+        layer.adjoint_info = hd.admm_adjoint_info()
+        layer.adjoint_iterations = layer.polish_refine_iter + 1
+        bad = (layer.adjoint_info["status"] != _lib.PDPLQR_ADMM_ADJOINT_EXACT).nonzero()[0]
+        if bad.size and not layer.allow_unconverged:
+            b = int(bad[0])
+            why = ("the factorisation at the solution failed" if layer.adjoint_info["status"][b] ==
+                   _lib.PDPLQR_ADMM_ADJOINT_FAILED else "its polish was rejected or the solve did not converge")
+            raise RuntimeError(
+                f"BoxLQRLayer: problem {b} of the batch has no exact active-set gradient ({why}; "
+                "layer.adjoint_info, layer.admm_info).  Raise max_iter, tighten eps, or build the layer with "
+                "allow_unconverged=True.")
+        return (None,) + tuple(o.view(shp) if o is not None else None for o, shp in zip(outs, ctx.shapes))
+
 
 class BoxLQRLayer:
     """``ws = layer(E, c, H, h, x0, D, lb, ub)``: the optimum of
@@ -223,14 +248,35 @@ class BoxLQRLayer:
     (``admm_info["polish_status"]``: 1 accepted, 2 rejected), so a loose
     ``eps`` gives what thousands of iterations at a tight one gave.  The
     explicit x-update the backward pass differentiates through then runs at
-    the polished ``(w, y, z)``, which is a fixed point of the ADMM step."""
+    the polished ``(w, y, z)``, which is a fixed point of the ADMM step.
+
+    ``backward_mode``: ``"fixed_point"`` (the default) is the iteration above.
+    ``"active_set"`` (needs ``polish=True``) differentiates the optimum exactly
+    on the active set the polish guessed: ``backward`` is one
+    ``pdplqr_admm_adjoint`` call -- ``polish_refine_iter + 1`` solves on the
+    factor of the polishing system, no host round trip, accuracy independent
+    of ``eps`` and ``adj_tol`` -- and ``forward`` skips
+    the explicit x-update.  It raises ``RuntimeError`` naming the first problem
+    whose gradient is not exact (``adjoint_info["status"]`` != 1: polish
+    rejected, solve not converged, or a failed factorisation) unless
+    ``allow_unconverged``.  A row with ``lb == ub`` sends its whole gradient to
+    ``lb`` in this mode; the fixed-point mode sends it to both ``lb`` and ``ub``."""
 
     def __init__(self, n: int, m: int, N: int, batch: int, ncs, rho, sigma: float = 1e-6, alpha: float = 1.6,
                  eps: float = 1e-6, max_iter: int = 4000, adj_tol: float = 1e-8, adj_max_iter: int = 4000,
                  check_every: int = 25, allow_unconverged: bool = False, device: int = 0,
                  detect_infeasible: bool = False, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4,
-                 polish: bool = False, polish_delta: float = 1e-6, polish_refine_iter: int = 3):
+                 polish: bool = False, polish_delta: float = 1e-6, polish_refine_iter: int = 3,
+                 backward_mode: str = "fixed_point"):
         from .solvers import admm_settings
+
+        if backward_mode not in ("fixed_point", "active_set"):
+            raise ValueError('BoxLQRLayer: backward_mode is "fixed_point" or "active_set"')
+        if backward_mode == "active_set" and not polish:
+            raise ValueError('BoxLQRLayer: backward_mode="active_set" requires polish=True')
+        self.backward_mode = backward_mode
+        self.polish_refine_iter = int(polish_refine_iter)
+        self.adjoint_info = None
 
         self.n, self.m, self.N, self.batch = int(n), int(m), int(N), int(batch)
         self.sigma, self.alpha = float(sigma), float(alpha)

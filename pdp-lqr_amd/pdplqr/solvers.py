@@ -226,6 +226,29 @@ class _Handle:
         check(lib().pdplqr_adjoint_rows(self.h, *[p[0] for p in ps], _mem_of(*ps)))
         self._leave(cur)
 
+    def admm_adjoint(self, gws, gvs=None, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, glb=None, gub=None):
+        """Gradients of the box-constrained optimum of the last ``admm_solve``
+        (polish on) on its guessed active set (include/pdplqr.h:
+        pdplqr_admm_adjoint): ``gws`` = d loss / d ws, ``gvs`` = d loss /
+        d (D ws) or ``None``; outputs left ``None`` are not computed."""
+        objs = [gws, gvs, gE, gc, gH, gh, gx, gD, glb, gub]
+        names = ("gws", "gvs", "gE", "gc", "gH", "gh", "gx", "gD", "glb", "gub")
+        ps = [_ptr(o, nm) for o, nm in zip(objs, names)]
+        cur = self._enter(*objs)
+        check(lib().pdplqr_admm_adjoint(self.h, *[p[0] for p in ps], _mem_of(*ps)))
+        self._leave(cur)
+
+    def admm_adjoint_info(self):
+        """The last ``admm_adjoint``: ``status`` (1 exact, 2 approximate: the
+        polish was rejected or the solve did not end solved, 3 the
+        factorisation failed) and ``resid`` [batch][2]: max|D_a v| / max|v| after
+        the last refinement step and that step's relative change of v."""
+        st = np.zeros(self.batch, dtype=np.int32)
+        rs = np.zeros((self.batch, 2))
+        check(lib().pdplqr_admm_adjoint_info(self.h, st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             C.c_void_p(rs.ctypes.data)))
+        return {"status": st, "resid": rs}
+
     def clear_workspace(self):
         check(lib().pdplqr_clear_workspace(self.h))
 
@@ -592,6 +615,15 @@ class BatchedLQRSolver:
         """The same after a penalised x-update (``ncs`` > 0): also d loss /
         d (D, g, rho), with ``gvs`` = d loss / d (D ws); see pdplqr_adjoint_rows."""
         self._hd.adjoint_rows(ws, rho, gws, gvs, gE, gc, gH, gh, gx, gD, gg, grho)
+
+    def admm_adjoint(self, gws, gvs=None, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, glb=None, gub=None):
+        """d loss / d (E, c, H, h, x0, D, lb, ub) of the optimum the last
+        ``admm_solve`` (polish on) returned, exact on its active set; see
+        pdplqr_admm_adjoint."""
+        self._hd.admm_adjoint(gws, gvs, gE, gc, gH, gh, gx, gD, glb, gub)
+
+    def admm_adjoint_info(self):
+        return self._hd.admm_adjoint_info()
 
     def synchronize(self):
         self._hd.synchronize()
