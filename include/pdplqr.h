@@ -223,6 +223,27 @@ int pdplqr_get_value_function(pdplqr_handle h, int32_t b, int32_t k, double *P, 
 int pdplqr_adjoint(pdplqr_handle h, const double *ws, const double *gws, double *gE, double *gc, double *gH,
                    double *gh, double *gx, int mem);
 
+/* pdplqr_adjoint for a PARALLEL (segmented) handle (new).  Arguments, layouts,
+ * the NULL-skips-work rule and the gradients are pdplqr_adjoint's (gH with
+ * respect to the symmetric matrix, exactly symmetric, sigma not in it); `ws`
+ * is the solution of the problem the handle last factored (it need not come
+ * from this handle's forward, and no forward has to precede the call).  The
+ * adjoint solution costs one segmented backward_without_factorization and one
+ * segmented forward (log depth in the horizon); the per-stage costates, which
+ * a PARALLEL handle does not cache, are recovered by one wave per device
+ * segment walking back from the boundary costates of the suffix scans, in a
+ * form whose rounding does not grow along a segment.
+ * PARALLEL solver of either condensed type, keep_factors = 1, one device, no
+ * constraint rows, nx + nu <= 64 (PDPLQR_ERR_UNSUPPORTED otherwise); needs a
+ * preceding pdplqr_backward, and a handle driven by the pdplqr_shard_* calls
+ * must hold the last shard (PDPLQR_ERR_STATE); NULL ws or gws is
+ * PDPLQR_ERR_INVALID.  A refused call writes nothing.  The handle's state is
+ * unchanged: forward returns the bits it returned before, and
+ * update_problem_data -> backward_without_factorization -> forward behave as
+ * if the call had not happened.  Device buffers: nothing waits for the device. */
+int pdplqr_adjoint_parallel(pdplqr_handle h, const double *ws, const double *gws, double *gE, double *gc,
+                            double *gH, double *gh, double *gx, int mem);
+
 /* The adjoint of the penalised x-update (new): pdplqr_adjoint for handles with
  * constraint rows.  The handle last factored
  *     H~_k = H_k + sigma I + D_k^T R D_k,   h~_k = h_k - sigma wbar_k - D_k^T R g_k

@@ -21,6 +21,31 @@ int launch_adjoint_lu(const Shape &sh, double *KD, double *buf, bool restore, hi
 size_t adjoint_lds_bytes(const Shape &sh, int ts);
 int adjoint_tile(const Shape &sh);
 
+// pdplqr_adjoint_parallel (adjoint_parallel.hip, kernels_adjoint_parallel.hip): the
+// per-stage costates of both solves on a PARALLEL handle, one wave per
+// (problem, device segment), and the gradient pass reading them
+struct SegCostateArgs {
+    Shape sh;
+    int S;                               // device segments per problem
+    const int32_t *seg_start, *seg_len;  // [S]
+    const double *E, *FR;                // model, rollout records [b][N][s m + m]
+    const double *Lc;                    // the segment-local P_k, packed lower n x n at stage offset k ps
+    const double *lpc, *lpa;             // lp_k = [lu'; p_k] of the primal and of the adjoint solve
+    const double *ws, *v;                // primal and adjoint solutions [b][N*s + n]
+    const double *sufp, *sufa;           // suffix scans of both solves [b][S][es]
+    double *lam, *mu;                    // out: costates [b][N + 1][n] (entry 0: segment 0's lambda_0, mu_0)
+    int need_lam;                        // 0: lam is not stored
+};
+int launch_seg_costate(const SegCostateArgs &a, hipStream_t st);
+struct AdjointCostateArgs {
+    Shape sh;
+    const double *ws, *v;     // primal and adjoint solutions [b][N*s + n]
+    const double *lam, *mu;   // costates [b][N + 1][n]
+    double *gE, *gc, *gH, *gh, *gx;  // outputs in the boundary layouts; NULL = not wanted
+    int ts = 0;               // stages per block (set by the launcher)
+};
+int launch_adjoint_grad_costate(const AdjointCostateArgs &a, hipStream_t st);
+
 // pdplqr_adjoint_rows: the gradients of the constraint rows (kernels_adjoint_rows.hip)
 struct AdjointRowsArgs {
     Shape sh;

@@ -125,6 +125,7 @@ namespace pdplqr { struct ParallelState;
 struct KKTState;
 struct AdmmState;
 struct AdjointState;
+struct ParAdjointState;
 struct MultiDev;
 // one slice of a num_devices split (multidev.hip)
 struct MdSlice {
@@ -177,6 +178,7 @@ struct pdplqr_handle_s {
     pdplqr::KKTState *kkt = nullptr;       // KKT solver state (kkt.hip)
     pdplqr::AdmmState *admm = nullptr;     // ADMM outer loop state (admm.hip), allocated on first use
     pdplqr::AdjointState *adj = nullptr;   // pdplqr_adjoint scratch (adjoint.hip), allocated on first use
+    pdplqr::ParAdjointState *padj = nullptr;  // pdplqr_adjoint_parallel scratch (adjoint_parallel.hip), on first use
     int admm_iters = 0;                    // iterations of the last admm_solve
     int admm_rho_updates = 0;              // adaptive-rho refactorizations of the last admm_solve
     // pdplqr_admm_set_infeasibility_detection (admm.hip, kernels_infeas.hip)

@@ -25,24 +25,10 @@
 #include <algorithm>
 
 #include "adjoint.hpp"
+#include "adjoint_store.hpp"
 #include "device_common.hpp"
 
 namespace pdplqr {
-
-template <bool VEC, class F>
-__device__ __forceinline__ void store_run(double *dst, int cnt, F &&val) {
-    const int tid = threadIdx.x;
-    if (VEC) {
-        for (int e = 2 * tid; e < cnt; e += 512) {
-            d2v x;
-            x.x = val(e);
-            x.y = val(e + 1);
-            gstore2(dst + e, x);
-        }
-    } else {
-        for (int e = tid; e < cnt; e += 256) gstore(dst + e, val(e));
-    }
-}
 
 template <int NN, int MM, bool VEC>
 __global__ __launch_bounds__(256) void k_adjoint_grad(AdjointArgs A) {

@@ -239,13 +239,32 @@ int launch_riccati_forward_seg_xl(const Shape &sh, const double *E, const double
 // Host side of the PARALLEL solver (parallel_host.hip), as solvers.hip drives it.
 int parallel_init(pdplqr_handle h);      // state, device segments, buffers
 void parallel_release(pdplqr_handle h);
+// Buffers one solve takes in place of the handle's own (pdplqr_adjoint_parallel:
+// another right-hand side on the cached factors); a null member keeps the
+// handle's.  The boundary maps, vfun, xhat and lam stay the handle's: every
+// forward rebuilds them from the elements, the scan and x0.
+struct ParallelSub {
+    const double *c = nullptr, *hw = nullptr;  // model offsets and linear cost terms
+    double *lpc = nullptr;                     // where the nofact recursion writes lp_k
+    double *elem = nullptr;                    // segment elements (F, C, P already there; f, p written)
+    double *bufA = nullptr, *bufB = nullptr;   // the suffix scan's ping-pong
+    int *flag = nullptr;                       // the scans' / maps' failure flag [b]
+    const double *suf_final = nullptr;         // out (parallel_backward): where this solve's scan ended
+};
 // segment backward + suffix scan; `last_is_terminal` = 0 for a non-final
 // horizon shard.
-int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact = true);
+int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact = true, ParallelSub *sub = nullptr);
 // condensed forward: boundary maps under the suffix value functions, their
 // prefix composition (ceil(log2 (S + 1)) rounds), then the segment rollouts
 int parallel_forward(pdplqr_handle h, const double *x0, double *ws, const double *left, const double *right,
-                     int last_is_terminal, long long rstride = 0);
+                     int last_is_terminal, long long rstride = 0, const ParallelSub *sub = nullptr);
+// the device segments, the elements and the suffix scan of the last backward
+struct ParallelView {
+    int S;
+    const int32_t *seg_start, *seg_len;  // device, [S]
+    const double *elem, *suf_final;      // [b][S][es]
+};
+void parallel_view(pdplqr_handle h, ParallelView &v);
 int parallel_status(pdplqr_handle h, int32_t *flags);  // per-problem status (host)
 // the device flags parallel_status reads: seg_status [b][S], flag [b]
 void parallel_status_view(pdplqr_handle h, const int32_t **seg_status, int *S, const int32_t **flag);

@@ -216,18 +216,20 @@ void parallel_release(pdplqr_handle h) {
 
 // inclusive suffix scan of the segment elements (ceil(log2 S) rounds): entry i
 // is the value function at the start of segment i
-static int parallel_scans(pdplqr_handle h, int last_is_terminal) {
+static int parallel_scans(pdplqr_handle h, int last_is_terminal, ParallelSub *sub) {
     ParallelState *ps = h->par;
     const Shape &sh = h->sh;
-    const double *sin = ps->elem;
-    double *bufs[2] = {ps->bufA, ps->bufB};
+    const double *sin = sub && sub->elem ? sub->elem : ps->elem;
+    double *const bufA = sub && sub->bufA ? sub->bufA : ps->bufA;
+    double *bufs[2] = {bufA, sub && sub->bufB ? sub->bufB : ps->bufB};
+    const double *&suf_final = sub ? sub->suf_final : ps->suf_final;
     int round = 0;
     const bool r4 = ps->scan4 != nullptr;  // two rounds per launch (k_seg_scan4)
     ScanArgs s;  // what every round shares
     s.n = sh.n;
     s.S = ps->S;
     s.terminal = last_is_terminal;
-    s.flag = ps->flag;
+    s.flag = sub && sub->flag ? sub->flag : ps->flag;
     s.lu = h->cfg.condensed_type == PDPLQR_CONDENSED_LU;
     s.mw = sh.mw;
     s.xlw = h->xl_ws;
@@ -236,13 +238,13 @@ static int parallel_scans(pdplqr_handle h, int last_is_terminal) {
         // Sklansky rounds: the first into bufA, the later ones in place there
         for (int d = 1; d < ps->S; d <<= 1) {
             s.dist = d;
-            s.in = d == 1 ? sin : ps->bufA;
-            s.out = ps->bufA;
+            s.in = d == 1 ? sin : bufA;
+            s.out = bufA;
             s.sk = d == 1 ? 1 : 2;
             int rc = launch_seg_scan(s, sh.batch, h->stream);
             if (rc) return rc;
         }
-        ps->suf_final = ps->bufA;
+        suf_final = bufA;
         return PDPLQR_OK;
     }
     s.scratch = ps->scan4;
@@ -254,11 +256,11 @@ static int parallel_scans(pdplqr_handle h, int last_is_terminal) {
         if (rc) return rc;
         sin = s.out;
     }
-    ps->suf_final = sin;
+    suf_final = sin;
     return PDPLQR_OK;
 }
 
-int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact) {
+int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact, ParallelSub *sub) {
     ParallelState *ps = h->par;
     const Shape &sh = h->sh;
     SegArgs a;
@@ -268,32 +270,32 @@ int parallel_backward(pdplqr_handle h, int last_is_terminal, bool fact) {
     a.seg_len = ps->seg_len;
     a.last_is_terminal = last_is_terminal;
     a.E = h->E;
-    a.c = h->c;
+    a.c = sub && sub->c ? sub->c : h->c;
     a.Hw = h->Hw;
-    a.hw = h->hw;
+    a.hw = sub && sub->hw ? sub->hw : h->hw;
     a.FR = h->KD;
     a.G = ps->G;
     a.Lc = h->Lc;
-    a.lpc = h->lpc;
-    a.elem = ps->elem;
+    a.lpc = sub && sub->lpc ? sub->lpc : h->lpc;
+    a.elem = sub && sub->elem ? sub->elem : ps->elem;
     a.seg_status = ps->seg_status;
-    a.flag = ps->flag;  // reset by the segment backward itself
+    a.flag = sub && sub->flag ? sub->flag : ps->flag;  // reset by the segment backward itself
     a.xlw = h->xl_ws;
     a.xl_grid = ps->xl_grid;
     int rc = fact ? launch_seg_backward(a, h->stream) : launch_seg_backward_nofact(a, h->stream);
     if (rc) return rc;
-    return parallel_scans(h, last_is_terminal);
+    return parallel_scans(h, last_is_terminal, sub);
 }
 
 int parallel_forward(pdplqr_handle h, const double *x0, double *ws, const double *left, const double *right,
-                     int last_is_terminal, long long rstride) {
+                     int last_is_terminal, long long rstride, const ParallelSub *sub) {
     ParallelState *ps = h->par;
     const Shape &sh = h->sh;
     MapArgs ma;
     ma.n = sh.n;
     ma.S = ps->S;
-    ma.elem = ps->elem;
-    ma.suf = ps->suf_final;
+    ma.elem = sub && sub->elem ? sub->elem : ps->elem;
+    ma.suf = sub ? sub->suf_final : ps->suf_final;
     ma.left = left;
     ma.right = right;
     ma.rstride = rstride;
@@ -302,7 +304,7 @@ int parallel_forward(pdplqr_handle h, const double *x0, double *ws, const double
     ma.vfun = ps->vfun;
     ma.xhat = ps->xhat;
     ma.lam = ps->lam;
-    ma.flag = ps->flag;
+    ma.flag = sub && sub->flag ? sub->flag : ps->flag;
     ma.lu = h->cfg.condensed_type == PDPLQR_CONDENSED_LU;
     ma.mw = sh.mw;
     ma.xlw = h->xl_ws;
@@ -335,7 +337,16 @@ int parallel_forward(pdplqr_handle h, const double *x0, double *ws, const double
     sf.G = ps->G;
     sf.xhat = ps->xhat;
     sf.lam = ps->lam;
-    return launch_riccati_forward_seg(sh, h->E, h->c, h->KD, sf, ws, h->stream);
+    return launch_riccati_forward_seg(sh, h->E, sub && sub->c ? sub->c : h->c, h->KD, sf, ws, h->stream);
+}
+
+void parallel_view(pdplqr_handle h, ParallelView &v) {
+    const ParallelState *ps = h->par;
+    v.S = ps->S;
+    v.seg_start = ps->seg_start;
+    v.seg_len = ps->seg_len;
+    v.elem = ps->elem;
+    v.suf_final = ps->suf_final;
 }
 
 int parallel_status(pdplqr_handle h, int32_t *flags) {

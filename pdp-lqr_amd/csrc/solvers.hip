@@ -33,6 +33,7 @@ void solver_release(pdplqr_handle h) {
     graph_release(h);
     admm_release(h);
     adjoint_release(h);
+    adjoint_parallel_release(h);
     parallel_release(h);
     kkt_release(h);
 }

@@ -17,6 +17,7 @@ int solver_backward_nofact(pdplqr_handle h, const double *rho);
 int solver_backward_prepared(pdplqr_handle h);
 void admm_release(pdplqr_handle h);  // admm.hip
 void adjoint_release(pdplqr_handle h);  // adjoint.hip
+void adjoint_parallel_release(pdplqr_handle h);  // adjoint_parallel.hip
 struct AdmmArgs;
 int solver_nofact_admm(pdplqr_handle h, const AdmmArgs &a, bool check);
 int solver_forward(pdplqr_handle h, const double *x0, double *ws);

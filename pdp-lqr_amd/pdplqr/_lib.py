@@ -51,6 +51,7 @@ EXPORTS = [
     "pdplqr_admm_check_certificates",
     "pdplqr_admm_set_polish", "pdplqr_admm_polish_info", "pdplqr_admm_kkt_residuals",
     "pdplqr_admm_adjoint", "pdplqr_admm_adjoint_info",
+    "pdplqr_adjoint_parallel",
 ]
 
 
@@ -140,6 +141,8 @@ def lib() -> C.CDLL:
         L.pdplqr_admm_kkt_residuals.argtypes = [vp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_adjoint"):  # (absent from older A/B variants)
         L.pdplqr_adjoint.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
+    if hasattr(L, "pdplqr_adjoint_parallel"):  # (absent from older A/B variants)
+        L.pdplqr_adjoint_parallel.argtypes = [vp, dp, dp, dp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_adjoint_rows"):  # (absent from older A/B variants)
         L.pdplqr_adjoint_rows.argtypes = [vp] + [dp] * 12 + [C.c_int]
     if hasattr(L, "pdplqr_admm_adjoint"):  # (absent from older A/B variants)

@@ -7,9 +7,10 @@ optimum ``ws`` of
     min sum 1/2 w_k^T (H_k + sigma I) w_k + h_k^T w_k
     s.t. x_{k+1} = E_k w_k + c_k,  x_0 = x0
 
-on the serial HIP solver, and is differentiable once: ``backward`` is one call
-of ``pdplqr_adjoint`` (an extra solve on the cached factor plus one streamed
-gradient pass), which writes only the gradients autograd asks for.  ``H`` is
+on the serial HIP solver (or, with ``solver="parallel"``, the segmented one),
+and is differentiable once: ``backward`` is one call of ``pdplqr_adjoint``
+(``pdplqr_adjoint_parallel``): an extra solve on the cached factor plus one
+streamed gradient pass, which writes only the gradients autograd asks for.  ``H`` is
 taken as symmetric; its gradient is the one with respect to the symmetric
 matrix.  There is no CPU path.
 
@@ -55,23 +56,39 @@ class _LQRSolve(torch.autograd.Function):
         (ws,) = ctx.saved_tensors
         outs = [torch.empty(layer.batch, cnt, dtype=torch.float64, device=layer._dev) if need else None
                 for cnt, need in zip(layer._per, ctx.needs_input_grad[1:])]
-        layer._hd.adjoint(ws, gws.contiguous(), *outs)
+        adjoint = layer._hd.adjoint_parallel if layer.solver == "parallel" else layer._hd.adjoint
+        adjoint(ws, gws.contiguous(), *outs)
         return (None,) + tuple(o.view(shp) if o is not None else None for o, shp in zip(outs, ctx.shapes))
 
 
 class LQRLayer:
-    """``ws = layer(E, c, H, h, x0)``; owns a serial keep_factors handle.
+    """``ws = layer(E, c, H, h, x0)``; owns a keep_factors handle.
+
+    ``solver="serial"`` (the default) solves on the batched serial kernels and
+    differentiates with ``pdplqr_adjoint``.  ``solver="parallel"`` cuts the
+    horizon into segments (``num_segments``, ``segment_len``, ``condensed`` as
+    for ``BatchedLQRSolver``) and differentiates with
+    ``pdplqr_adjoint_parallel``: the choice for one long-horizon problem.
 
     The handle holds ONE factorization: call ``backward`` on a result before
     the layer is called again (a later ``backward`` raises ``RuntimeError``)."""
 
-    def __init__(self, n: int, m: int, N: int, batch: int, device: int = 0, sigma: float = 0.0):
+    def __init__(self, n: int, m: int, N: int, batch: int, device: int = 0, sigma: float = 0.0,
+                 solver: str = "serial", num_segments: int = 2, segment_len: int = 0, condensed: str = "CHOLESKY"):
         self.n, self.m, self.N, self.batch, self.sigma = int(n), int(m), int(N), int(batch), float(sigma)
+        if solver not in ("serial", "parallel"):
+            raise ValueError(f"LQRLayer: solver must be 'serial' or 'parallel', not {solver!r}")
+        self.solver = solver
         s = n + m
         # doubles per problem of E, c, H, h (= ws), x0
         self._per = (N * n * s, N * n, N * s * s + n * n, N * s + n, n)
         self._dev = torch.device("cuda", int(device))
-        self._hd = _Handle(n, m, N, batch, _lib.PDPLQR_SOLVER_SERIAL, device=device, keep_factors=True)
+        if solver == "parallel":
+            ct = {"LU": _lib.PDPLQR_CONDENSED_LU, "CHOLESKY": _lib.PDPLQR_CONDENSED_CHOLESKY}[condensed]
+            self._hd = _Handle(n, m, N, batch, _lib.PDPLQR_SOLVER_PARALLEL, num_segments=num_segments,
+                               condensed_type=ct, device=device, keep_factors=True, segment_len=segment_len)
+        else:
+            self._hd = _Handle(n, m, N, batch, _lib.PDPLQR_SOLVER_SERIAL, device=device, keep_factors=True)
         self._wbar = torch.zeros(batch, self._per[3], dtype=torch.float64, device=self._dev)  # proximal centre
         self._gen = 0
 

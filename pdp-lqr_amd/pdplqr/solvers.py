@@ -213,6 +213,15 @@ class _Handle:
         check(lib().pdplqr_adjoint(self.h, *[p[0] for p in ps], _mem_of(*ps)))
         self._leave(cur)
 
+    def adjoint_parallel(self, ws, gws, gE=None, gc=None, gH=None, gh=None, gx=None):
+        """``adjoint`` on a PARALLEL handle (include/pdplqr.h:
+        pdplqr_adjoint_parallel): the same arguments and gradients."""
+        objs = [ws, gws, gE, gc, gH, gh, gx]
+        ps = [_ptr(o, nm) for o, nm in zip(objs, ("ws", "gws", "gE", "gc", "gH", "gh", "gx"))]
+        cur = self._enter(*objs)
+        check(lib().pdplqr_adjoint_parallel(self.h, *[p[0] for p in ps], _mem_of(*ps)))
+        self._leave(cur)
+
     def adjoint_rows(self, ws, rho, gws, gvs=None, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, gg=None,
                      grho=None):
         """``adjoint`` for a handle with constraint rows (include/pdplqr.h:
@@ -609,6 +618,12 @@ class BatchedLQRSolver:
         """d loss / d (E, c, H, h, x0) from gws = d loss / d ws (serial solver,
         keep_factors=True, after backward + forward); see pdplqr_adjoint."""
         self._hd.adjoint(ws, gws, gE, gc, gH, gh, gx)
+
+    def adjoint_parallel(self, ws, gws, gE=None, gc=None, gH=None, gh=None, gx=None):
+        """``adjoint`` for a ``solver="parallel"`` handle (keep_factors=True,
+        after backward): the adjoint solve runs segmented, at log depth in
+        the horizon; see pdplqr_adjoint_parallel."""
+        self._hd.adjoint_parallel(ws, gws, gE, gc, gH, gh, gx)
 
     def adjoint_rows(self, ws, rho, gws, gvs=None, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, gg=None,
                      grho=None):
