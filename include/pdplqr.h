@@ -524,6 +524,46 @@ int pdplqr_admm_adjoint(pdplqr_handle h, const double *gws, const double *gvs, d
 /* PDPLQR_ERR_STATE before any pdplqr_admm_adjoint.                           */
 int pdplqr_admm_adjoint_info(pdplqr_handle h, int32_t *status, double *resid);
 
+/* ---------------------------------------------------------------------- */
+/* Second-order cone rows of the ADMM loop (new).  Some of   */
+/* a stage's constraint rows form cones: the z-update of admm_solve then    */
+/* projects onto the mixed set (box rows: clamp; the rows of a cone, with   */
+/* p = v - lb: |x| <= t keeps p, |x| <= -t gives 0, otherwise (a |x|, a x)  */
+/* with a = (1 + t / |x|) / 2; |x| is the square root of the squares summed */
+/* in row order, without rescaling).  Everything else of the iteration --   */
+/* the y and w updates, the termination test, the freezing of converged     */
+/* problems, adaptive rho (a cone counts as an active row when its          */
+/* projection's argument had |x| >= t), admm_info, admm_status -- is         */
+/* unchanged, and a handle with no cones set launches what it launched      */
+/* before.  Examples: |u_k| <= u_max is the rows [0; I_m 0] with             */
+/* lb = (-u_max, 0, ..); a terminal ball |x_N| <= r the same on stage N.    */
+/* ---------------------------------------------------------------------- */
+
+/* cones of the handle's constraint rows, shared by the batch (host arrays, copied).
+ * Cone i covers rows [cone_row[i], cone_row[i] + cone_dim[i]) of stage cone_stage[i]
+ * (0..N; row indices are within the stage).  For those rows, with v = D_k w_k and b = lb:
+ *     v - b  in  K_q = { (t, x) : |x|_2 <= t },  first row = t
+ * ub of a cone row is not read (it still has to pass the existing lb <= ub check: pass ub = lb).
+ * Rows in no cone stay box rows.  num_cones = 0 clears.
+ * PDPLQR_ERR_INVALID: cone_dim < 2, a stage outside 0..N, a cone that leaves its stage's
+ * rows, overlapping or unsorted cones (order: stage, then row).  PDPLQR_ERR_UNSUPPORTED: a
+ * KKT handle (its softened dynamics make the split a different problem), num_devices > 1
+ * or a non-NULL `devices`, nx + nu > 64, cone_dim > nx + nu + 1 (nx + 1 at the terminal
+ * stage).  A refused call leaves the previous cones in place.
+ * With cones set, pdplqr_admm_solve returns PDPLQR_ERR_UNSUPPORTED while infeasibility
+ * detection or polish is on (hence pdplqr_admm_adjoint too), PDPLQR_ERR_INVALID when rho is
+ * not constant within a cone (the projection is Euclidean only then; the adaptive rule
+ * scales per problem and keeps it constant) or a cone row's lb is not finite (|lb| >= 1e20
+ * included) -- a refused solve writes nothing to ws, ys, zs -- and
+ * pdplqr_admm_kkt_residuals / pdplqr_admm_check_certificates return PDPLQR_ERR_UNSUPPORTED
+ * (they would read cone rows as boxes). */
+int pdplqr_admm_set_cones(pdplqr_handle h, int32_t num_cones, const int32_t *cone_stage,
+                          const int32_t *cone_row, const int32_t *cone_dim);
+/* out = the projection of v onto the handle's constraint set (box rows: clamp; cone rows:
+ * b + P_K(v - b)); v, lb, ub, out [batch][ny] in `mem`; needs only create (+ set_cones). */
+int pdplqr_admm_project(pdplqr_handle h, const double *v, const double *lb, const double *ub,
+                        double *out, int mem);
+
 /* Device info helpers (for hosts that do not link HIP). */
 int pdplqr_device_count(int32_t *count);
 

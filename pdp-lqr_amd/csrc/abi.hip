@@ -297,6 +297,7 @@ int pdplqr_destroy(pdplqr_handle h) {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     solver_release(h);
+    if (h->cone_buf) (void)hipFree(h->cone_buf);  // pdplqr_admm_set_cones
     free_all(h);
     delete h;
     return PDPLQR_OK;

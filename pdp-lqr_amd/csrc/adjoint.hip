@@ -270,6 +270,9 @@ extern "C" int pdplqr_admm_adjoint(pdplqr_handle h, const double *gws, const dou
         return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint needs a SERIAL handle (PARALLEL and KKT are not supported)");
     const Shape &sh = h->sh;
     if (sh.s > 64) return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint: n + m > 64 is not supported");
+    if (h->num_cones > 0)
+        return fail(PDPLQR_ERR_UNSUPPORTED,
+                    "admm_adjoint: the active-set adjoint is a statement about box rows; the handle has cones");
     if (sh.ny == 0)
         return fail(PDPLQR_ERR_UNSUPPORTED, "admm_adjoint: the handle has no constraint rows (use pdplqr_adjoint)");
     if (!h->cfg.keep_factors || !h->Lc || !h->lpc)

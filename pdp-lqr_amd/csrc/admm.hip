@@ -48,6 +48,9 @@
 // After the loop, opt-in (pdplqr_admm_set_polish): OSQP's polish (its section
 // 4) as refine_iter + 1 more x-updates of the same protocol on the guessed
 // active rows (admm_polish below, kernels_polish.hip).
+// Opt-in (pdplqr_admm_set_cones): some rows of a stage form second-order cones
+// D w - e_lb in K_q; the z-update projects onto the mixed set and the update
+// pass is k_admm_update_cone (kernels_cone.hip), nothing else changes.
 #include <algorithm>
 
 #include "admm.hpp"
@@ -879,6 +882,12 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
         return PDPLQR_ERR_INVALID;
     }
     if (h->md) return md_admm_solve(h, st, x0, lb, ub, rho, ws, ys, zs, mem);
+    const bool cones = h->num_cones > 0;
+    if (cones && (h->infeas_on || h->polish_on)) {
+        set_error("admm_solve: infeasibility detection and polish are statements about box rows; switch them off "
+                  "on a handle with cones (pdplqr_admm_set_cones)");
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
     if (int brc = bind_device(h)) return brc;
     int rc = admm_alloc(h);
     if (rc) return rc;
@@ -888,6 +897,21 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
     if ((rc = admm_begin(h, S, mem == PDPLQR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, x0, lb, ub,
                          rho, ws, ys, zs)))
         return rc;
+    if (cones) {
+        // rho constant within a cone (the projection is Euclidean only then), e_lb finite on cone rows
+        PDPLQR_HIP_TRY(hipMemsetAsync(s->active, 0, 2 * sizeof(int32_t), S));
+        if ((rc = launch_cone_validate(sh.batch, sh.ny, h->num_cones, h->cone_y0, h->cone_dim, s->lb, s->rho, s->active,
+                                       S)))
+            return rc;
+        PDPLQR_HIP_TRY(hipMemcpyAsync(s->active_h, s->active, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, S));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+        if (s->active_h[0] != 0 || s->active_h[1] != 0) {
+            set_error("admm_solve: " + std::to_string(s->active_h[0]) +
+                      " cones with rho not constant over their rows, " + std::to_string(s->active_h[1]) +
+                      " cone rows whose e_lb is not finite (|e_lb| >= 1e20)");
+            return PDPLQR_ERR_INVALID;
+        }
+    }
     // infeasibility detection (off: nothing below launches or copies anything new)
     const bool detect = h->infeas_on != 0;
     const bool det_p = detect && Y > 0 && h->eps_prim_inf > 0.0, det_d = detect && Y > 0 && h->eps_dual_inf > 0.0;
@@ -926,6 +950,7 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
     a.gw = h->gw;
     a.d_off = h->d_off;
     a.y_off = h->y_off;
+    ConeArgs ca{a, h->cone_off, h->cone_row, h->cone_dim};  // (read with cones set only)
     // KKT with the factor cache: the update pass also forms the next h~ = h - sigma w
     // and g (the KKT path takes rho through g in its backward, no penalty in h~)
     const bool kkt_lin = kkt && kkt_linear_supported(h);
@@ -935,9 +960,9 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
     int it = 1;
     bool refactor = true;  // iteration 1, and after an adaptive rho change
     bool fused = false;    // this iteration's backward already ran inside the fused update
-    bool can_fuse = !kkt && Y > 0 && h->Lc != nullptr;  // cleared when the fused kernel does not apply
+    bool can_fuse = !kkt && Y > 0 && h->Lc != nullptr && !cones;  // cleared when the fused kernel does not apply
     // KKT (Riccati-ordered 12/4, C5 rows): rollout + update fused (cleared when it does not apply)
-    bool can_fuse_kkt = kkt && kkt_ric_active(h) && a.uni == 4;
+    bool can_fuse_kkt = kkt && kkt_ric_active(h) && a.uni == 4 && !cones;
     int rho_updates = 0;
     for (;; ++it) {
         // x-update: the reference protocol (iteration 1 and after a rho
@@ -1001,7 +1026,12 @@ int pdplqr_admm_solve(pdplqr_handle h, const pdplqr_admm_settings *st, const dou
             else if (rc == PDPLQR_ERR_UNSUPPORTED) can_fuse = false;
             else return rc;
         }
-        if (!fused && (rc = launch_admm_update(a, admm_lps(sh), fuse, check, ugrid, ublk, S))) return rc;
+        if (cones) {
+            ca.a = a;
+            if ((rc = launch_admm_update_cone(ca, admm_lps(sh), fuse, check, S))) return rc;
+        } else if (!fused && (rc = launch_admm_update(a, admm_lps(sh), fuse, check, ugrid, ublk, S))) {
+            return rc;
+        }
         if (check) {
             // the certificates on the problems the termination test left iterating
             // (solved takes precedence); a certified one leaves `active`
@@ -1137,6 +1167,10 @@ int pdplqr_admm_check_certificates(pdplqr_handle h, const double *x0, const doub
         set_error(why);
         return PDPLQR_ERR_UNSUPPORTED;
     }
+    if (h->num_cones > 0) {
+        set_error("admm_check_certificates: the certificates read every row as a box row; the handle has cones");
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
     if (!h->model_set) {
         set_error("admm_check_certificates before set_model");
         return PDPLQR_ERR_STATE;
@@ -1231,6 +1265,10 @@ int pdplqr_admm_kkt_residuals(pdplqr_handle h, const double *x0, const double *l
         set_error(std::string("kkt_residuals / ") + why);
         return PDPLQR_ERR_UNSUPPORTED;
     }
+    if (h->num_cones > 0) {
+        set_error("admm_kkt_residuals: the row residual reads every row as a box row; the handle has cones");
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
     if (!h->model_set) {
         set_error("admm_kkt_residuals before set_model");
         return PDPLQR_ERR_STATE;
@@ -1261,6 +1299,116 @@ int pdplqr_admm_kkt_residuals(pdplqr_handle h, const double *x0, const double *l
     if ((rc = launch_kkt_residual(q, S))) return rc;
     if (mem != PDPLQR_MEM_DEVICE) {
         PDPLQR_HIP_TRY(hipMemcpyAsync(measures, bm.p, B * 4 * sizeof(double), hipMemcpyDeviceToHost, S));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    }
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_set_cones(pdplqr_handle h, int32_t num_cones, const int32_t *cone_stage, const int32_t *cone_row,
+                          const int32_t *cone_dim) {
+    if (!h || num_cones < 0 || (num_cones > 0 && (!cone_stage || !cone_row || !cone_dim))) {
+        set_error("set_cones: null handle / arrays or num_cones < 0");
+        return PDPLQR_ERR_INVALID;
+    }
+    const Shape &sh = h->sh;
+    // the list itself: sorted by (stage, row), disjoint, inside its stage's rows
+    int pk = -1, pend = 0;
+    for (int i = 0; i < num_cones; ++i) {
+        const int k = cone_stage[i], r = cone_row[i], d = cone_dim[i];
+        if (d < 2 || k < 0 || k > sh.N || r < 0 || (long long)r + d > h->ncs[k]) {
+            set_error("set_cones: cone " + std::to_string(i) + ": cone_dim < 2, stage outside 0..N, or rows outside "
+                      "the stage's rows");
+            return PDPLQR_ERR_INVALID;
+        }
+        if (k < pk || (k == pk && r < pend)) {
+            set_error("set_cones: cone " + std::to_string(i) + " overlaps its predecessor or is out of order "
+                      "(order: stage, then row)");
+            return PDPLQR_ERR_INVALID;
+        }
+        pk = k;
+        pend = r + d;
+    }
+    if (num_cones > 0) {
+        const char *why = nullptr;
+        if (h->cfg.solver == PDPLQR_SOLVER_KKT)
+            why = "set_cones: the KKT solver softens the dynamics by rho_dyn; SERIAL and PARALLEL only";
+        else if (h->md) why = "set_cones: num_devices handles are not supported";
+        else if (sh.s > 64) why = "set_cones: nx + nu <= 64 only";
+        for (int i = 0; i < num_cones && !why; ++i)
+            if (cone_dim[i] > (cone_stage[i] < sh.N ? sh.s : sh.n) + 1)
+                why = "set_cones: a cone over more rows than its stage has variables plus one";
+        if (why) {
+            set_error(why);
+            return PDPLQR_ERR_UNSUPPORTED;
+        }
+    }
+    if (h->md) {  // (num_cones = 0: nothing was ever set)
+        return PDPLQR_OK;
+    }
+    if (int brc = bind_device(h)) return brc;
+    int32_t *buf = nullptr;
+    if (num_cones > 0) {
+        const size_t no = (size_t)sh.N + 2, nc = (size_t)num_cones;
+        std::vector<int32_t> tab(no + 3 * nc, 0);
+        for (int i = 0; i < num_cones; ++i) {
+            ++tab[cone_stage[i] + 1];
+            tab[no + i] = cone_row[i];
+            tab[no + nc + i] = cone_dim[i];
+            tab[no + 2 * nc + i] = h->y_off_h[cone_stage[i]] + cone_row[i];
+        }
+        for (size_t k = 0; k + 1 < no; ++k) tab[k + 1] += tab[k];  // counts -> offsets (tab[N + 1] = num_cones)
+        if (hipMalloc((void **)&buf, tab.size() * sizeof(int32_t)) != hipSuccess) {
+            set_error("set_cones: hipMalloc failed");
+            return PDPLQR_ERR_ALLOC;
+        }
+        // an admm_solve in flight on the stream still reads the previous table
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = hipMemcpy(buf, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            set_error(std::string("set_cones: ") + hipGetErrorString(e));
+            return PDPLQR_ERR_HIP;
+        }
+        h->cone_off = buf;
+        h->cone_row = buf + no;
+        h->cone_dim = buf + no + nc;
+        h->cone_y0 = buf + no + 2 * nc;
+    } else {
+        PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
+        h->cone_off = h->cone_row = h->cone_dim = h->cone_y0 = nullptr;
+    }
+    if (h->cone_buf) (void)hipFree(h->cone_buf);
+    h->cone_buf = buf;
+    h->num_cones = num_cones;
+    return PDPLQR_OK;
+}
+
+int pdplqr_admm_project(pdplqr_handle h, const double *v, const double *lb, const double *ub, double *out, int mem) {
+    if (!h) return PDPLQR_ERR_INVALID;
+    if (h->md) {
+        set_error("admm_project: num_devices handles are not supported");
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
+    const Shape &sh = h->sh;
+    const size_t Y = (size_t)sh.batch * sh.ny;
+    if (Y == 0) return PDPLQR_OK;
+    if (!v || !lb || !ub || !out) {
+        set_error("admm_project: null v / lb / ub / out");
+        return PDPLQR_ERR_INVALID;
+    }
+    if (int brc = bind_device(h)) return brc;
+    hipStream_t S = h->stream;
+    int rc;
+    CallBuf<double> bv, bl, bu, bo;
+    if ((rc = bv.in(v, Y, mem, S)) || (rc = bl.in(lb, Y, mem, S)) || (rc = bu.in(ub, Y, mem, S)) ||
+        (rc = bo.in(nullptr, Y, mem, S)))
+        return rc;
+    if (mem == PDPLQR_MEM_DEVICE) bo.p = out;
+    if ((rc = launch_cone_project(sh, h->y_off, h->num_cones > 0 ? h->cone_off : nullptr, h->cone_row, h->cone_dim,
+                                  bv.p, bl.p, bu.p, bo.p, S)))
+        return rc;
+    if (mem != PDPLQR_MEM_DEVICE) {
+        PDPLQR_HIP_TRY(hipMemcpyAsync(out, bo.p, Y * sizeof(double), hipMemcpyDeviceToHost, S));
         PDPLQR_HIP_TRY(hipStreamSynchronize(S));
     }
     return PDPLQR_OK;

@@ -51,6 +51,25 @@ __device__ __forceinline__ void admm_decide(const AdmmArgs &a, int b, double rp,
     a.rscale[b] = f;
 }
 
+// Second-order cone rows (kernels_cone.hip).  The
+// handle's cone table on the device: the cones of stage k are entries
+// c_off[k] .. c_off[k + 1] - 1 of (c_row, c_dim), in row order; cone i covers
+// rows [c_row[i], c_row[i] + c_dim[i]) of its stage.
+struct ConeArgs {
+    AdmmArgs a;
+    const int32_t *c_off, *c_row, *c_dim;
+};
+// k_admm_update with the cone projection on the cone rows (lps 16 / 32 / 64)
+int launch_admm_update_cone(const ConeArgs &c, int lps, bool fuse, bool check, hipStream_t st);
+// out = the projection of v onto the mixed set, all [batch][ny] (c_off null: every row a box row)
+int launch_cone_project(const Shape &sh, const int32_t *y_off, const int32_t *c_off, const int32_t *c_row,
+                        const int32_t *c_dim, const double *v, const double *lb, const double *ub, double *out,
+                        hipStream_t st);
+// flag[0] += cones whose rho is not constant, flag[1] += cone rows whose e_lb is
+// not finite; c_y0[i] is the first row of cone i within a problem's ny rows
+int launch_cone_validate(int batch, int ny, int num_cones, const int32_t *c_y0, const int32_t *c_dim, const double *lb,
+                         const double *rho, int32_t *flag, hipStream_t st);
+
 // Infeasibility certificates (kernels_infeas.hip).  The
 // vectors tested are y - yp and w - wp (the loop: differences of consecutive
 // iterates) or y and w themselves (yp, wp null: the stand-alone evaluator).

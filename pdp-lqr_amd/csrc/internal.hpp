@@ -188,6 +188,11 @@ struct pdplqr_handle_s {
     int polish_on = 0;
     double polish_delta = 1e-6;
     int polish_refine = 3;
+    // pdplqr_admm_set_cones (admm.hip, kernels_cone.hip): one device block
+    // [off (N + 2) | row | dim | y0] of num_cones entries each, freed by pdplqr_destroy
+    int num_cones = 0;
+    int32_t *cone_buf = nullptr;
+    const int32_t *cone_off = nullptr, *cone_row = nullptr, *cone_dim = nullptr, *cone_y0 = nullptr;
     int shard_last = 1;  // last shard_backward's is_last_shard
     pdplqr::MultiDev *md = nullptr;  // num_devices > 1 (multidev.hip): the slices' handles
     // replayable launch sequences of backward / backward_without_factorization /

@@ -52,6 +52,7 @@ EXPORTS = [
     "pdplqr_admm_set_polish", "pdplqr_admm_polish_info", "pdplqr_admm_kkt_residuals",
     "pdplqr_admm_adjoint", "pdplqr_admm_adjoint_info",
     "pdplqr_adjoint_parallel",
+    "pdplqr_admm_set_cones", "pdplqr_admm_project",
 ]
 
 
@@ -148,6 +149,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "pdplqr_admm_adjoint"):  # (absent from older A/B variants)
         L.pdplqr_admm_adjoint.argtypes = [vp] + [dp] * 10 + [C.c_int]
         L.pdplqr_admm_adjoint_info.argtypes = [vp, ip, dp]
+    if hasattr(L, "pdplqr_admm_set_cones"):  # (absent from older A/B variants)
+        L.pdplqr_admm_set_cones.argtypes = [vp, i32, ip, ip, ip]
+        L.pdplqr_admm_project.argtypes = [vp, dp, dp, dp, dp, C.c_int]
     if hasattr(L, "pdplqr_multidev_plan"):  # (absent from pre-round-4 A/B variants)
         L.pdplqr_multidev_plan.argtypes = [i32, i32, ip, i32, i32, C.POINTER(C.c_int64)]
     for nm in EXPORTS:

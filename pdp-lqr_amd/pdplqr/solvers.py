@@ -356,6 +356,38 @@ class _Handle:
         self._leave(cur)
         return meas
 
+    def set_cones(self, cones):
+        """Declare second-order cones over the handle's constraint rows
+        (include/pdplqr.h: pdplqr_admm_set_cones): ``cones`` is a sequence of
+        ``(stage, row, dim)`` sorted by stage, then row; rows ``row .. row + dim - 1``
+        of that stage ask ``D w - lb`` in ``{(t, x): |x| <= t}``.  An empty
+        sequence clears them."""
+        tab = np.ascontiguousarray(np.asarray(list(cones), dtype=np.int32).reshape(-1, 3).T)
+        i32 = C.POINTER(C.c_int32)
+        check(lib().pdplqr_admm_set_cones(self.h, int(tab.shape[1]), tab[0].ctypes.data_as(i32),
+                                          tab[1].ctypes.data_as(i32), tab[2].ctypes.data_as(i32)))
+
+    def project(self, v, lb, ub):
+        """The projection of ``v`` onto the handle's constraint set
+        (pdplqr_admm_project): box rows clamp to ``[lb, ub]``, the rows of a cone
+        give ``lb + P_K(v - lb)``.  Host (numpy) or device (torch) inputs
+        ``[batch][ny]``; returns the result in the same memory."""
+        objs = [v, lb, ub]
+        ps = [_ptr(o, nm) for o, nm in zip(objs, ("v", "lb", "ub"))]
+        mem = _mem_of(*ps)
+        if mem == _lib.PDPLQR_MEM_DEVICE:
+            import torch
+
+            out = torch.empty_like(v)
+            po = C.c_void_p(out.data_ptr())
+        else:
+            out = np.empty_like(v)
+            po = C.c_void_p(out.ctypes.data)
+        cur = self._enter(*objs, out)
+        check(lib().pdplqr_admm_project(self.h, *[p[0] for p in ps], po, mem))
+        self._leave(cur)
+        return out
+
     def set_infeasibility_detection(self, enable: bool, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
         """Switch OSQP's infeasibility certificates of ``admm_solve`` on or off
         (include/pdplqr.h: pdplqr_admm_set_infeasibility_detection)."""
@@ -682,6 +714,17 @@ class BatchedLQRSolver:
 
     def kkt_residuals(self, x0, lb, ub, ws, ys):
         return self._hd.kkt_residuals(x0, lb, ub, ws, ys)
+
+    def set_cones(self, cones):
+        """Second-order cones over the constraint rows for the following
+        ``admm_solve`` calls: a sequence of ``(stage, row, dim)``; empty clears
+        (see pdplqr_admm_set_cones)."""
+        self._hd.set_cones(cones)
+
+    def project(self, v, lb, ub):
+        """The projection of ``v [batch][ny]`` onto the constraint set (boxes
+        and cones); see pdplqr_admm_project."""
+        return self._hd.project(v, lb, ub)
 
     def value_function(self, b, k):
         return self._hd.value_function(b, k)
