@@ -563,6 +563,63 @@ int pdplqr_admm_set_cones(pdplqr_handle h, int32_t num_cones, const int32_t *con
  * b + P_K(v - b)); v, lb, ub, out [batch][ny] in `mem`; needs only create (+ set_cones). */
 int pdplqr_admm_project(pdplqr_handle h, const double *v, const double *lb, const double *ub,
                         double *out, int mem);
+/* The transposed Jacobian of that projection at v applied to gout, the cotangent of its
+ * output: gv = J^T gout, and glb, gub the cotangents of the bounds; all [batch][ny] in
+ * `mem`, any of the three outputs may be NULL.  Box rows: gv = gout where lb < v < ub, else
+ * 0; glb = gout where v <= lb; gub = gout where v >= ub (a row with lb == ub gives both).
+ * Cone rows, with p = v - lb = (t, x), r = |x| and g = (g_t, g_x): the case is the one
+ * pdplqr_admm_project takes for the same bits; r <= t: J = I; r <= -t: J = 0; otherwise,
+ * with xh = x / r and d = xh . g_x,
+ *     (J g)_t = (g_t + d) / 2,   (J g)_x = (g_t xh + (1 + t / r) g_x - (t / r) d xh) / 2
+ * (J is symmetric).  gv = J g, glb = g - J g, gub = 0.  Needs only create (+ set_cones),
+ * changes no handle state; the limits and error codes of pdplqr_admm_project. */
+int pdplqr_admm_project_vjp(pdplqr_handle h, const double *v, const double *lb, const double *ub,
+                            const double *gout, double *gv, double *glb, double *gub, int mem);
+
+/* ---------------------------------------------------------------------- */
+/* The fixed-point adjoint of the ADMM loop on the device, box rows and     */
+/* cone rows alike (new).  At a fixed point (w, y, z) of     */
+/* the iteration the gradient of a loss on w is the limit of                 */
+/*     a <- dl/ds + J_step^T a,   a = (a_w, a_y, a_z) from 0,                */
+/* J_step the Jacobian of one ADMM step.  With tt = zs + ys / rho (the       */
+/* projection's argument at the fixed point) and P^T the operator of         */
+/* pdplqr_admm_project_vjp at tt, one iteration is                            */
+/*     b_w = gws + a_w;  q = a_z - rho o a_y;  b_vr = rho o a_y + P^T q       */
+/*     (dh, dg) = pdplqr_adjoint_rows' (gh, gg) for gws := alpha b_w,         */
+/*                gvs := alpha b_vr (one solve on the cached factor)         */
+/*     a_w <- (1 - alpha) b_w - sigma dh                                      */
+/*     a_y <- a_y + P^T q / rho - dg / rho                                    */
+/*     a_z <- (1 - alpha) b_vr + dg                                           */
+/* Every check_every iterations (and at max_iter) a problem whose max-norm   */
+/* change of a is <= tol times the max-norm of a is frozen; the loop ends    */
+/* when none is active (one small device-to-host read per test) or at        */
+/* max_iter.  One last adjoint pass at the final cotangents writes gE, gc,   */
+/* gH, gh, gx, gD in pdplqr_adjoint_rows' layouts; glb, gub [batch][ny]      */
+/* follow pdplqr_admm_project_vjp with gout := q (box rows: q where          */
+/* tt <= lb / tt >= ub; cone rows: glb = q - P^T q, gub = 0).  Any output    */
+/* may be NULL.                                                               */
+/* On entry the preconditions of pdplqr_adjoint_rows hold: the handle last   */
+/* factored the x-update at (w, y, z) with `rho`, and ws is the w~ its       */
+/* forward returned.  ys, zs, lb, ub, rho [batch][ny]; gws [batch][N*s+n];   */
+/* sigma, alpha the solve's.  Limits: those of pdplqr_adjoint_rows (SERIAL,  */
+/* keep_factors = 1, one device, nx + nu <= 64, rows within the rows         */
+/* kernel's LDS tile) and at least one constraint row, else                  */
+/* PDPLQR_ERR_UNSUPPORTED; PDPLQR_ERR_STATE before backward;                 */
+/* PDPLQR_ERR_INVALID for null inputs, bad settings (0 < alpha < 2, sigma,   */
+/* tol >= 0, max_iter, check_every >= 1) or rho not constant within a cone.  */
+/* A refused call writes nothing.  The handle's factor, record and lp are    */
+/* unchanged.                                                                 */
+/* ---------------------------------------------------------------------- */
+int pdplqr_admm_adjoint_fixed_point(pdplqr_handle h, const double *ws, const double *ys, const double *zs,
+                                    const double *lb, const double *ub, const double *rho, const double *gws,
+                                    double sigma, double alpha, double tol, int32_t max_iter, int32_t check_every,
+                                    double *gE, double *gc, double *gH, double *gh, double *gx, double *gD,
+                                    double *glb, double *gub, int mem);
+
+/* The last pdplqr_admm_adjoint_fixed_point, host arrays, any may be NULL: iters [batch]    */
+/* (the iteration of the problem's last test), converged [batch], resid [batch][2]: the     */
+/* max-norm change and the max-norm of a at that test.  PDPLQR_ERR_STATE before any call.   */
+int pdplqr_admm_adjoint_fixed_point_info(pdplqr_handle h, int32_t *iters, int32_t *converged, double *resid);
 
 /* Device info helpers (for hosts that do not link HIP). */
 int pdplqr_device_count(int32_t *count);

@@ -35,9 +35,18 @@ struct AdjointState {
     double *resid = nullptr;                // [b][2]
     int32_t *stat = nullptr;                // [b] PDPLQR_ADMM_ADJOINT_*
     bool as_ran = false;                    // an admm_adjoint got as far as its launches
+    // pdplqr_admm_adjoint_fixed_point (allocated by its first call)
+    double *fa_w = nullptr, *fa_y = nullptr, *fa_z = nullptr;  // the state a
+    double *fjq = nullptr, *fgvs = nullptr;  // P^T q; alpha b_vr of the final pass
+    double *fresid = nullptr;                // [b][2]
+    int32_t *fint = nullptr;                 // [4 + 3 b]: active, the validation's two counts | done | conv | iters
+    int32_t *factive_h = nullptr;            // pinned copy of fint[0..2]
+    double *fin[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // host ys, zs, lb, ub, rho, gws staged
+    bool fp_ran = false;                     // an admm_adjoint_fixed_point got as far as its loop
 };
 
 void adjoint_release(pdplqr_handle h) {
+    if (h->adj && h->adj->factive_h) (void)hipHostFree(h->adj->factive_h);
     delete h->adj;
     h->adj = nullptr;
 }
@@ -465,4 +474,217 @@ extern "C" int pdplqr_debug_asadj_rows(pdplqr_handle h, double *gD, double *glb,
     ra.ts = plan.ts;
     ra.max_rows = plan.max_rows;
     return launch_asadj_rows(ra, h->y_off_h.data(), h->d_off_h.data(), h->stream);
+}
+
+// k_fpadj_step's arguments: the handle's rows and cone table, the scratch's state and
+// flags, the call's six vectors in[] = (ys, zs, lb, ub, rho, gws) on the device
+static FpadjArgs fpadj_args(pdplqr_handle h, const double *const in[6], double sigma, double alpha, double tol) {
+    AdjointState *s = h->adj;
+    const long long B = h->sh.batch;
+    FpadjArgs q{};
+    q.sh = h->sh;
+    q.D = h->D;
+    q.ys = in[0];
+    q.zs = in[1];
+    q.lb = in[2];
+    q.ub = in[3];
+    q.rho = in[4];
+    q.gws = in[5];
+    q.d_off = h->d_off;
+    q.y_off = h->y_off;
+    q.c_off = h->num_cones > 0 ? h->cone_off : nullptr;
+    q.c_row = h->cone_row;
+    q.c_dim = h->cone_dim;
+    q.max_nc = h->max_nc;
+    q.alpha = alpha;
+    q.sigma = sigma;
+    q.tol = tol;
+    q.aw = s->fa_w;
+    q.ay = s->fa_y;
+    q.az = s->fa_z;
+    q.jq = s->fjq;
+    q.rhs = s->rhs;
+    q.active = s->fint;
+    q.done = s->fint + 4;
+    q.conv = q.done + B;
+    q.iters = q.conv + B;
+    q.resid = s->fresid;
+    return q;
+}
+
+// The fixed-point adjoint of the ADMM loop at its solution, box rows and cone
+// rows alike (include/pdplqr.h): per iteration one
+// adjoint solve on the cached factor and one k_fpadj_step, which forms the
+// next right-hand side itself; every check_every iterations one 4-byte read
+// tells whether any problem is still active.  The last solve's gradients are
+// pdplqr_adjoint_rows' passes at the final cotangents.
+extern "C" int pdplqr_admm_adjoint_fixed_point(pdplqr_handle h, const double *ws, const double *ys, const double *zs,
+                                               const double *lb, const double *ub, const double *rho,
+                                               const double *gws, double sigma, double alpha, double tol,
+                                               int32_t max_iter, int32_t check_every, double *gE, double *gc,
+                                               double *gH, double *gh, double *gx, double *gD, double *glb,
+                                               double *gub, int mem) {
+    const char *nm = "admm_adjoint_fixed_point";
+    auto bad = [&](int code, const char *why) { return fail(code, (std::string(nm) + ": " + why).c_str()); };
+    if (!h) return bad(PDPLQR_ERR_INVALID, "null handle");
+    if (h->md) return bad(PDPLQR_ERR_UNSUPPORTED, "multi-device handles are not supported");
+    if (h->cfg.solver != PDPLQR_SOLVER_SERIAL)
+        return bad(PDPLQR_ERR_UNSUPPORTED, "needs a SERIAL handle (PARALLEL and KKT are not supported)");
+    const Shape &sh = h->sh;
+    if (sh.s > 64) return bad(PDPLQR_ERR_UNSUPPORTED, "n + m > 64 is not supported");
+    if (sh.ny == 0) return bad(PDPLQR_ERR_UNSUPPORTED, "the handle has no constraint rows (use pdplqr_adjoint)");
+    if (!h->cfg.keep_factors) return bad(PDPLQR_ERR_UNSUPPORTED, "requires keep_factors = 1");
+    if (!ws || !ys || !zs || !lb || !ub || !rho || !gws)
+        return bad(PDPLQR_ERR_INVALID, "null ws / ys / zs / lb / ub / rho / gws");
+    if (!(alpha > 0.0 && alpha < 2.0) || !(sigma >= 0.0) || !(tol >= 0.0) || max_iter < 1 || check_every < 1)
+        return bad(PDPLQR_ERR_INVALID, "bad settings (0 < alpha < 2, sigma >= 0, tol >= 0, max_iter >= 1, check_every >= 1)");
+    if (!h->Lc || !h->lpc || !h->factored) return bad(PDPLQR_ERR_STATE, "called before backward");
+    if (h->rec_gain) return bad(PDPLQR_ERR_STATE, "the rollout record is not in factor form");
+    if (int brc = bind_device(h)) return brc;
+    AdjointRowsArgs ra;
+    if (!adjoint_rows_plan(sh, h->y_off_h.data(), h->d_off_h.data(), ra))
+        return bad(PDPLQR_ERR_UNSUPPORTED, "the constraint rows of one stage exceed the kernel's LDS tile");
+    int rc = adjoint_alloc(h);
+    if (rc) return rc;
+    AdjointState *s = h->adj;
+    const long long B = sh.batch, Y = B * sh.ny, W = B * sh.perh;
+    // first use; every pointer is guarded on its own, so a call after a failed allocation takes up where that one stopped
+    if ((!s->fa_w && (rc = dev_alloc(h, &s->fa_w, W))) || (!s->fa_y && (rc = dev_alloc(h, &s->fa_y, Y))) ||
+        (!s->fa_z && (rc = dev_alloc(h, &s->fa_z, Y))) || (!s->fjq && (rc = dev_alloc(h, &s->fjq, Y))) ||
+        (!s->fgvs && (rc = dev_alloc(h, &s->fgvs, Y))) || (!s->fresid && (rc = dev_alloc(h, &s->fresid, 2 * B))) ||
+        (!s->fint && (rc = dev_alloc(h, &s->fint, 4 + 3 * B))))
+        return rc;
+    if (!s->factive_h) {
+        int32_t *pin = nullptr;
+        PDPLQR_HIP_TRY(hipHostMalloc((void **)&pin, 3 * sizeof(int32_t), hipHostMallocDefault));
+        s->factive_h = pin;
+    }
+    const bool dev = mem == PDPLQR_MEM_DEVICE;
+    hipStream_t st = h->stream;
+
+    // inputs: read in place on the device, staged from the host
+    const double *dws, *din[6];
+    if ((rc = stage_in(h, ws, h->st_ws, W, mem, &dws))) return rc;
+    const double *const hin[6] = {ys, zs, lb, ub, rho, gws};
+    for (int i = 0; i < 6; ++i) {
+        const long long cnt = i < 5 ? Y : W;
+        if (!dev && !s->fin[i] && (rc = dev_alloc(h, &s->fin[i], cnt))) return rc;
+        if ((rc = stage_in(h, hin[i], s->fin[i], cnt, mem, &din[i]))) return rc;
+    }
+    int32_t *active = s->fint;
+    if (h->num_cones > 0) {
+        // rho constant within a cone (the projection is Euclidean only then), before anything is written
+        PDPLQR_HIP_TRY(hipMemsetAsync(active, 0, 3 * sizeof(int32_t), st));
+        if ((rc = launch_cone_validate(sh.batch, sh.ny, h->num_cones, h->cone_y0, h->cone_dim, din[2], din[4],
+                                       active + 1, st)))
+            return rc;
+        PDPLQR_HIP_TRY(hipMemcpyAsync(s->factive_h, active, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(st));
+        if (s->factive_h[1] != 0 || s->factive_h[2] != 0)
+            return bad(PDPLQR_ERR_INVALID, (std::to_string(s->factive_h[1]) + " cones with rho not constant over their "
+                       "rows, " + std::to_string(s->factive_h[2]) + " cone rows whose lb is not finite").c_str());
+    }
+    // outputs: the caller's device pointers, or staging allocated on first use
+    double *const user[8] = {gE, gc, gH, gh, gx, gD, glb, gub};
+    const long long cnt[8] = {B * sh.perE, B * sh.perc, B * sh.perH, W, B * sh.n, B * sh.ndD, Y, Y};
+    double *out[8];
+    for (int i = 0; i < 8; ++i) {
+        out[i] = cnt[i] > 0 ? user[i] : nullptr;
+        if (out[i] && !dev) {
+            if (!s->out[i] && (rc = dev_alloc(h, &s->out[i], cnt[i]))) return rc;
+            out[i] = s->out[i];
+        }
+    }
+
+    // a = 0: the first cotangents are (gws, 0, 0)
+    PDPLQR_HIP_TRY(hipMemsetAsync(s->fa_w, 0, (size_t)W * sizeof(double), st));
+    PDPLQR_HIP_TRY(hipMemsetAsync(s->fa_y, 0, (size_t)Y * sizeof(double), st));
+    PDPLQR_HIP_TRY(hipMemsetAsync(s->fa_z, 0, (size_t)Y * sizeof(double), st));
+    PDPLQR_HIP_TRY(hipMemsetAsync(s->fresid, 0, (size_t)(2 * B) * sizeof(double), st));
+    PDPLQR_HIP_TRY(hipMemsetAsync(s->fint, 0, (size_t)(4 + 3 * B) * sizeof(int32_t), st));
+    s->fp_ran = true;
+    FpadjArgs q = fpadj_args(h, din, sigma, alpha, tol);
+    if ((rc = launch_fpadj_step(q, st))) return rc;
+
+    if ((rc = launch_adjoint_lu(sh, h->KD, s->lus, false, st))) return rc;
+    for (int it = 1; it <= max_iter && !rc; ++it) {
+        const bool test = it % check_every == 0 || it == max_iter;
+        if ((rc = adjoint_solve(h, s->rhs, s->v))) break;
+        if (test && hipMemsetAsync(active, 0, sizeof(int32_t), st) != hipSuccess) rc = PDPLQR_ERR_HIP;
+        q.v = s->v;
+        q.test = test ? 1 : 0;
+        q.it = it;
+        if (!rc) rc = launch_fpadj_step(q, st);
+        if (rc || !test) continue;
+        if (hipMemcpyAsync(s->factive_h, active, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            rc = fail(PDPLQR_ERR_HIP, "admm_adjoint_fixed_point: reading the active count failed");
+            break;
+        }
+        if (s->factive_h[0] == 0) break;
+    }
+    // the final pass: the cotangents' row vectors, then the solve the gradients are read from
+    const bool need_solve = out[0] || out[1] || out[2] || out[3] || out[4] || out[5];
+    if (!rc && (need_solve || out[6] || out[7])) {
+        q.v = nullptr;
+        q.test = 0;
+        q.gvs = s->fgvs;
+        q.glb = out[6];
+        q.gub = out[7];
+        rc = launch_fpadj_step(q, st);
+    }
+    if (!rc && need_solve) rc = adjoint_solve(h, s->rhs, s->v);
+    // the record's lu' goes back whatever the launches returned
+    const int rc2 = launch_adjoint_lu(sh, h->KD, s->lus, true, st);
+    if (rc || rc2) return rc ? rc : rc2;
+
+    if (need_solve) {
+        if ((rc = launch_adjoint_grad(adjoint_args(h, dws, out[0], out[1], out[2], out[3], out[4]), st))) return rc;
+        if (out[5]) {
+            adjoint_rows_args(h, ra, dws, din[4], s->fgvs, out[5], nullptr, nullptr);
+            if ((rc = launch_adjoint_rows(ra, h->y_off_h.data(), h->d_off_h.data(), st))) return rc;
+        }
+    }
+    if (!dev) {
+        for (int i = 0; i < 8; ++i)
+            if (out[i])
+                PDPLQR_HIP_TRY(hipMemcpyAsync(user[i], out[i], (size_t)cnt[i] * sizeof(double), hipMemcpyDeviceToHost, st));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(st));
+    }
+    h->host_staged = false;
+    return PDPLQR_OK;
+}
+
+extern "C" int pdplqr_admm_adjoint_fixed_point_info(pdplqr_handle h, int32_t *iters, int32_t *converged,
+                                                    double *resid) {
+    if (!h) return fail(PDPLQR_ERR_INVALID, "admm_adjoint_fixed_point_info: null handle");
+    if (!h->adj || !h->adj->fp_ran)
+        return fail(PDPLQR_ERR_STATE, "admm_adjoint_fixed_point_info before admm_adjoint_fixed_point");
+    if (int brc = bind_device(h)) return brc;
+    PDPLQR_HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t B = (size_t)h->sh.batch;
+    const int32_t *conv = h->adj->fint + 4 + B, *its = conv + B;
+    if (iters) PDPLQR_HIP_TRY(hipMemcpy(iters, its, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (converged) PDPLQR_HIP_TRY(hipMemcpy(converged, conv, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (resid) PDPLQR_HIP_TRY(hipMemcpy(resid, h->adj->fresid, 2 * B * sizeof(double), hipMemcpyDeviceToHost));
+    return PDPLQR_OK;
+}
+
+// Internal diagnostic (not part of include/pdplqr.h; scripts/cone_adjoint_bench.py):
+// k_fpadj_step alone, a middle iteration (state stepped, right-hand side
+// written, no test) on the state and the adjoint solution the last
+// pdplqr_admm_adjoint_fixed_point left in the scratch, every problem unfrozen.
+// The call's vectors are arguments (device pointers; nothing of an earlier
+// call's is kept).  The state is scratch: the next call starts it from zero.
+extern "C" int pdplqr_debug_fpadj_step(pdplqr_handle h, const double *ys, const double *zs, const double *lb,
+                                       const double *ub, const double *rho, const double *gws, double sigma,
+                                       double alpha) {
+    if (!h || !h->adj || !h->adj->fp_ran) return fail(PDPLQR_ERR_STATE, "debug_fpadj_step before admm_adjoint_fixed_point");
+    if (!ys || !zs || !lb || !ub || !rho || !gws) return fail(PDPLQR_ERR_INVALID, "debug_fpadj_step: null input");
+    if (int brc = bind_device(h)) return brc;
+    const double *const in[6] = {ys, zs, lb, ub, rho, gws};
+    FpadjArgs q = fpadj_args(h, in, sigma, alpha, 0.0);
+    PDPLQR_HIP_TRY(hipMemsetAsync(q.done, 0, (size_t)h->sh.batch * sizeof(int32_t), h->stream));
+    q.v = h->adj->v;
+    return launch_fpadj_step(q, h->stream);
 }

@@ -96,4 +96,25 @@ struct AsadjRowsArgs {
 };
 int launch_asadj_rows(const AsadjRowsArgs &a, const int32_t *y_off_h, const int32_t *d_off_h, hipStream_t st);
 
+// pdplqr_admm_adjoint_fixed_point: one iteration's elementwise work (kernels_fpadj.hip)
+struct FpadjArgs {
+    Shape sh;
+    const double *D;
+    const double *ys, *zs, *lb, *ub, *rho;  // the fixed point and the call's vectors, [b][ny]
+    const double *gws;                      // dl/dw [b][N*s + n]
+    const int32_t *d_off, *y_off;
+    const int32_t *c_off, *c_row, *c_dim;   // the handle's cone table (c_off NULL: no cones)
+    int max_nc;
+    double alpha, sigma, tol;
+    const double *v;            // this iteration's adjoint solution (NULL: no update, the cotangents only)
+    double *aw, *ay, *az;       // the state, stepped in place
+    double *jq;                 // [b][ny] P^T q at the state (read by the next update)
+    double *rhs;                // out: the next solve's right-hand side alpha b_w + D^T (alpha b_vr)
+    int test, it;               // a test iteration: the measures, done / conv / iters / active
+    int32_t *done, *conv, *iters, *active;
+    double *resid;              // [b][2]: the change and the norm of the problem's last test
+    double *gvs, *glb, *gub;    // the final pass (NULL: not wanted): alpha b_vr and the bounds' gradients
+};
+int launch_fpadj_step(const FpadjArgs &a, hipStream_t st);
+
 }  // namespace pdplqr

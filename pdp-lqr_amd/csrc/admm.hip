@@ -1414,4 +1414,42 @@ int pdplqr_admm_project(pdplqr_handle h, const double *v, const double *lb, cons
     return PDPLQR_OK;
 }
 
+int pdplqr_admm_project_vjp(pdplqr_handle h, const double *v, const double *lb, const double *ub, const double *gout,
+                            double *gv, double *glb, double *gub, int mem) {
+    if (!h) return PDPLQR_ERR_INVALID;
+    if (h->md) {
+        set_error("admm_project_vjp: num_devices handles are not supported");
+        return PDPLQR_ERR_UNSUPPORTED;
+    }
+    const Shape &sh = h->sh;
+    const size_t Y = (size_t)sh.batch * sh.ny;
+    if (Y == 0) return PDPLQR_OK;
+    if (!v || !lb || !ub || !gout) {
+        set_error("admm_project_vjp: null v / lb / ub / gout");
+        return PDPLQR_ERR_INVALID;
+    }
+    if (int brc = bind_device(h)) return brc;
+    hipStream_t S = h->stream;
+    const bool dev = mem == PDPLQR_MEM_DEVICE;
+    int rc;
+    CallBuf<double> bv, bl, bu, bg, bo[3];
+    if ((rc = bv.in(v, Y, mem, S)) || (rc = bl.in(lb, Y, mem, S)) || (rc = bu.in(ub, Y, mem, S)) ||
+        (rc = bg.in(gout, Y, mem, S)))
+        return rc;
+    double *const user[3] = {gv, glb, gub};
+    for (int i = 0; i < 3; ++i) {
+        if (dev) bo[i].p = user[i];
+        else if (user[i] && (rc = bo[i].in(nullptr, Y, mem, S))) return rc;
+    }
+    if ((rc = launch_cone_project_vjp(sh, h->y_off, h->num_cones > 0 ? h->cone_off : nullptr, h->cone_row, h->cone_dim,
+                                      bv.p, bl.p, bu.p, bg.p, bo[0].p, bo[1].p, bo[2].p, S)))
+        return rc;
+    if (!dev) {
+        for (int i = 0; i < 3; ++i)
+            if (user[i]) PDPLQR_HIP_TRY(hipMemcpyAsync(user[i], bo[i].p, Y * sizeof(double), hipMemcpyDeviceToHost, S));
+        PDPLQR_HIP_TRY(hipStreamSynchronize(S));
+    }
+    return PDPLQR_OK;
+}
+
 }  // extern "C"

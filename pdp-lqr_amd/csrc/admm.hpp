@@ -65,6 +65,11 @@ int launch_admm_update_cone(const ConeArgs &c, int lps, bool fuse, bool check, h
 int launch_cone_project(const Shape &sh, const int32_t *y_off, const int32_t *c_off, const int32_t *c_row,
                         const int32_t *c_dim, const double *v, const double *lb, const double *ub, double *out,
                         hipStream_t st);
+// gv = J^T gout, J the Jacobian of launch_cone_project at v; glb, gub the cotangents of the
+// bounds (any of the three NULL: not wanted)
+int launch_cone_project_vjp(const Shape &sh, const int32_t *y_off, const int32_t *c_off, const int32_t *c_row,
+                            const int32_t *c_dim, const double *v, const double *lb, const double *ub,
+                            const double *gout, double *gv, double *glb, double *gub, hipStream_t st);
 // flag[0] += cones whose rho is not constant, flag[1] += cone rows whose e_lb is
 // not finite; c_y0[i] is the first row of cone i within a problem's ny rows
 int launch_cone_validate(int batch, int ny, int num_cones, const int32_t *c_y0, const int32_t *c_dim, const double *lb,

@@ -24,12 +24,14 @@
 //                       butterflies: everything is in the tile) for z, y, g, the
 //                       three D^T column sums and the five maxima, in row order.
 //   k_cone_project      the projection onto the mixed set alone (pdplqr_admm_project)
+//   k_cone_project_vjp  its transposed Jacobian applied to a cotangent (pdplqr_admm_project_vjp)
 //   k_cone_validate     rho constant within a cone, e_lb finite on cone rows
 // The cone arithmetic is compiled with contraction off (a value does not depend
 // on the kernel instance, and k_cone_project gives the update's bits); the box
 // rows keep the contraction k_admm_update is compiled with, so that they keep
 // its bits (tests/test_gpu_cone.py pins both).
 #include "admm.hpp"
+#include "cone_math.hpp"
 #include "device_common.hpp"
 
 namespace pdplqr {
@@ -56,24 +58,6 @@ __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
     return v;
-}
-
-// which case p = (t, x) with |x| = nx falls in: 0 keep, 1 zero, 2 the boundary
-// point (head = a |x|, the tail scales by a)
-__device__ __forceinline__ int cone_case(double t, double nx, double &head, double &sc) {
-#pragma clang fp contract(off)
-    head = sc = 0.0;
-    if (nx <= t) return 0;
-    if (nx <= -t) return 1;
-    sc = (1.0 + t / nx) / 2.0;
-    head = sc * nx;
-    return 2;
-}
-
-// entry i of the projection of the cone's p
-__device__ __forceinline__ double cone_entry(int kind, double head, double sc, int i, double p) {
-#pragma clang fp contract(off)
-    return kind == 0 ? p : (kind == 1 ? 0.0 : (i == 0 ? head : sc * p));
 }
 
 }  // namespace
@@ -277,6 +261,60 @@ __global__ void __launch_bounds__(64) k_cone_project(Shape sh, const int32_t *__
     }
 }
 
+// The transposed Jacobian of k_cone_project at v applied to gout, on the same
+// walk: gv = J^T gout, glb and gub the cotangents of the bounds (any NULL).  A
+// box row passes gout to gv strictly inside, to glb where v <= lb, to gub where
+// v >= ub.  A cone takes the case k_cone_project takes for the same bits (the
+// same |x|, the same tests); out = b + Pi(v - b), so glb = g - J g and gub = 0.
+__global__ void __launch_bounds__(64) k_cone_project_vjp(Shape sh, const int32_t *__restrict__ y_off,
+                                                         const int32_t *__restrict__ c_off,
+                                                         const int32_t *__restrict__ c_row,
+                                                         const int32_t *__restrict__ c_dim, const double *v,
+                                                         const double *lb, const double *ub, const double *gout,
+                                                         double *gv, double *glb, double *gub) {
+#pragma clang fp contract(off)
+    const int k = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (k > sh.N) return;
+    const int yo = y_off[k], nc = y_off[k + 1] - yo;
+    const long long base = (long long)b * sh.ny + yo;
+    int ci = c_off ? c_off[k] : 0;
+    const int ce = c_off ? c_off[k + 1] : 0;
+    int r = 0;
+    while (r < nc) {
+        if (ci < ce && r == c_row[ci]) {
+            const int cd = c_dim[ci];
+            const double t = v[base + r] - lb[base + r];
+            double ss = 0.0;
+            for (int i = 1; i < cd; ++i) {
+                const double p = v[base + r + i] - lb[base + r + i];
+                ss = ss + p * p;
+            }
+            const double nx = sqrt(ss);
+            double head, sc;
+            const int kind = cone_case(t, nx, head, sc);
+            const double g0 = gout[base + r];
+            double d = 0.0;
+            if (kind == 2)
+                for (int i = 1; i < cd; ++i) d = d + ((v[base + r + i] - lb[base + r + i]) / nx) * gout[base + r + i];
+            for (int i = 0; i < cd; ++i) {
+                const double g = gout[base + r + i];
+                const double jg = cone_vjp_entry(kind, i, v[base + r + i] - lb[base + r + i], g, g0, d, t, nx);
+                if (gv) gv[base + r + i] = jg;
+                if (glb) glb[base + r + i] = g - jg;
+                if (gub) gub[base + r + i] = 0.0;
+            }
+            r += cd;
+            ++ci;
+        } else {
+            const double x = v[base + r], l = lb[base + r], u = ub[base + r], g = gout[base + r];
+            if (gv) gv[base + r] = (l < x && x < u) ? g : 0.0;
+            if (glb) glb[base + r] = x <= l ? g : 0.0;
+            if (gub) gub[base + r] = x >= u ? g : 0.0;
+            ++r;
+        }
+    }
+}
+
 // One thread per (cone, problem): flag[0] counts cones whose rho is not
 // constant, flag[1] cone rows whose e_lb is not finite (|e_lb| >= 1e20 is infinite)
 __global__ void k_cone_validate(int num_cones, int ny, const int32_t *__restrict__ c_y0,
@@ -325,6 +363,15 @@ int launch_cone_project(const Shape &sh, const int32_t *y_off, const int32_t *c_
                         hipStream_t st) {
     hipLaunchKernelGGL(k_cone_project, dim3((unsigned)sh.batch, (unsigned)(sh.N / 64 + 1)), dim3(64), 0, st, sh, y_off,
                        c_off, c_row, c_dim, v, lb, ub, out);
+    PDPLQR_HIP_TRY(hipGetLastError());
+    return PDPLQR_OK;
+}
+
+int launch_cone_project_vjp(const Shape &sh, const int32_t *y_off, const int32_t *c_off, const int32_t *c_row,
+                            const int32_t *c_dim, const double *v, const double *lb, const double *ub,
+                            const double *gout, double *gv, double *glb, double *gub, hipStream_t st) {
+    hipLaunchKernelGGL(k_cone_project_vjp, dim3((unsigned)sh.batch, (unsigned)(sh.N / 64 + 1)), dim3(64), 0, st, sh,
+                       y_off, c_off, c_row, c_dim, v, lb, ub, gout, gv, glb, gub);
     PDPLQR_HIP_TRY(hipGetLastError());
     return PDPLQR_OK;
 }

@@ -19,7 +19,7 @@ __version__ = "0.1.0"
 def __getattr__(name):
     # the torch layer (pdplqr/diff.py) is resolved on first use, so the package
     # itself still imports without torch
-    if name in ("LQRLayer", "BoxLQRLayer"):
+    if name in ("LQRLayer", "BoxLQRLayer", "ConeLQRLayer"):
         from . import diff
 
         return getattr(diff, name)

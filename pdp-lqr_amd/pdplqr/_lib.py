@@ -53,6 +53,7 @@ EXPORTS = [
     "pdplqr_admm_adjoint", "pdplqr_admm_adjoint_info",
     "pdplqr_adjoint_parallel",
     "pdplqr_admm_set_cones", "pdplqr_admm_project",
+    "pdplqr_admm_project_vjp", "pdplqr_admm_adjoint_fixed_point", "pdplqr_admm_adjoint_fixed_point_info",
 ]
 
 
@@ -152,6 +153,11 @@ def lib() -> C.CDLL:
     if hasattr(L, "pdplqr_admm_set_cones"):  # (absent from older A/B variants)
         L.pdplqr_admm_set_cones.argtypes = [vp, i32, ip, ip, ip]
         L.pdplqr_admm_project.argtypes = [vp, dp, dp, dp, dp, C.c_int]
+    if hasattr(L, "pdplqr_admm_adjoint_fixed_point"):  # (absent from older A/B variants)
+        L.pdplqr_admm_project_vjp.argtypes = [vp] + [dp] * 7 + [C.c_int]
+        L.pdplqr_admm_adjoint_fixed_point.argtypes = ([vp] + [dp] * 7 + [C.c_double] * 3 + [i32, i32] + [dp] * 8
+                                                      + [C.c_int])
+        L.pdplqr_admm_adjoint_fixed_point_info.argtypes = [vp, ip, ip, dp]
     if hasattr(L, "pdplqr_multidev_plan"):  # (absent from pre-round-4 A/B variants)
         L.pdplqr_multidev_plan.argtypes = [i32, i32, ip, i32, i32, C.POINTER(C.c_int64)]
     for nm in EXPORTS:

@@ -341,3 +341,81 @@ class BoxLQRLayer:
 
     def close(self):
         self._hd.close()
+
+
+class _ConeLQRSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, E, c, H, h, x0, D, lb, ub):
+        # BoxLQRLayer's forward protocol in its fixed-point mode (the solve from a zero start, then the
+        # explicit x-update at the returned point); the handle projects onto the layer's cones
+        return _BoxLQRSolve.forward(ctx, layer, E, c, H, h, x0, D, lb, ub)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gws):
+        layer = ctx.layer
+        if ctx.gen != layer._gen:
+            raise RuntimeError(
+                "ConeLQRLayer: backward through a solution whose factorization is gone: the layer was called again "
+                f"(call {layer._gen}) after the call being differentiated (call {ctx.gen}), and its handle keeps "
+                "one factorization.  Call backward before the next forward, or use one ConeLQRLayer per live graph.")
+        if not ctx.converged and not layer.allow_unconverged:
+            raise RuntimeError(
+                "ConeLQRLayer: the ADMM solve being differentiated did not converge for every problem of the batch "
+                "(layer.admm_info); the fixed-point adjoint is meaningless there.  Raise max_iter, loosen eps, or "
+                "build the layer with allow_unconverged=True.")
+        wt, ys, zs, lb, ub = ctx.saved_tensors
+        outs = [torch.empty(layer.batch, cnt, dtype=torch.float64, device=layer._dev) if nd else None
+                for cnt, nd in zip(layer._per, ctx.needs_input_grad[1:])]
+        hd = layer._hd
+        hd.admm_adjoint_fixed_point(wt, ys, zs, lb, ub, layer._rho, gws.contiguous(), layer.sigma, layer.alpha,
+                                    layer.adj_tol, layer.adj_max_iter, layer.check_every, *outs)
+        layer.adjoint_info = hd.admm_adjoint_fixed_point_info()
+        layer.adjoint_iterations = int(layer.adjoint_info["iters"].max())
+        return (None,) + tuple(o.view(shp) if o is not None else None for o, shp in zip(outs, ctx.shapes))
+
+
+class ConeLQRLayer(BoxLQRLayer):
+    """``ws = layer(E, c, H, h, x0, D, lb, ub)``: ``BoxLQRLayer``'s problem with
+    some rows of a stage forming second-order cones,
+
+        min sum 1/2 w_k^T H_k w_k + h_k^T w_k
+        s.t. x_{k+1} = E_k w_k + c_k,  x_0 = x0,
+             lb <= D w <= ub on the rows in no cone,
+             (D w - lb) in {(t, x): |x| <= t} on the rows of each cone,
+
+    differentiable once in all eight inputs.  ``cones`` is a list of
+    ``(stage, row, dim)`` as for ``set_cones`` (sorted by stage, then row; an
+    empty list gives ``BoxLQRLayer``'s problem); ``ub`` of a cone row is not
+    read and its gradient is zero.  ``rho`` must be constant within a cone.
+
+    A ``BoxLQRLayer`` in its fixed-point mode (its constructor, argument checks
+    and forward: ``pdplqr_admm_solve`` from a zero start at the fixed ``rho``,
+    then the explicit x-update at the returned point) whose handle carries the
+    cones and whose backward is ONE ``pdplqr_admm_adjoint_fixed_point`` call:
+    the fixed-point adjoint of DESIGN.md section 5.11 iterated on the device
+    until every problem's max-norm change is at most ``adj_tol`` times its
+    max-norm (tested every ``check_every`` iterations; a problem that passes is
+    frozen) or ``adj_max_iter``, writing only the gradients autograd asks for.
+    The gradients are those of the optimum where the projection is
+    differentiable (no cone argument on a face or at the apex, box rows
+    strictly complementary).  ``backward`` raises ``RuntimeError`` if a problem
+    did not converge (unless ``allow_unconverged``) or the layer was called
+    again in between (the handle keeps ONE factorization).  ``admm_info`` holds
+    the last solve's outcome, ``adjoint_info`` the last backward's per-problem
+    ``iters`` / ``converged`` / ``resid``, ``adjoint_iterations`` its largest
+    iteration count.  Polish, infeasibility detection and the active-set
+    backward are statements about box rows and are not offered here."""
+
+    def __init__(self, n: int, m: int, N: int, batch: int, ncs, rho, cones=(), sigma: float = 1e-6,
+                 alpha: float = 1.6, eps: float = 1e-6, max_iter: int = 4000, adj_tol: float = 1e-8,
+                 adj_max_iter: int = 4000, check_every: int = 25, allow_unconverged: bool = False, device: int = 0):
+        super().__init__(n, m, N, batch, ncs, rho, sigma=sigma, alpha=alpha, eps=eps, max_iter=max_iter,
+                         adj_tol=adj_tol, adj_max_iter=adj_max_iter, check_every=check_every,
+                         allow_unconverged=allow_unconverged, device=device)
+        self.cones = [tuple(int(x) for x in cn) for cn in cones]
+        if self.cones:
+            self._hd.set_cones(self.cones)
+
+    def __call__(self, E, c, H, h, x0, D, lb, ub):
+        return _ConeLQRSolve.apply(self, E, c, H, h, x0, D, lb, ub)

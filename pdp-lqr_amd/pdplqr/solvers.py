@@ -388,6 +388,57 @@ class _Handle:
         self._leave(cur)
         return out
 
+    def project_vjp(self, v, lb, ub, gout, want=("gv", "glb", "gub")):
+        """The transposed Jacobian of ``project`` at ``v`` applied to ``gout``,
+        the cotangent of its output (pdplqr_admm_project_vjp): a dict of those
+        of ``gv``, ``glb``, ``gub`` named in ``want``, ``[batch][ny]`` in the
+        inputs' memory.  Changes no handle state."""
+        objs = [v, lb, ub, gout]
+        ps = [_ptr(o, nm) for o, nm in zip(objs, ("v", "lb", "ub", "gout"))]
+        mem = _mem_of(*ps)
+        if mem == _lib.PDPLQR_MEM_DEVICE:
+            import torch
+
+            outs = {k: torch.empty_like(v) for k in want}
+            po = [C.c_void_p(outs[k].data_ptr()) if k in outs else None for k in ("gv", "glb", "gub")]
+        else:
+            outs = {k: np.empty_like(v) for k in want}
+            po = [C.c_void_p(outs[k].ctypes.data) if k in outs else None for k in ("gv", "glb", "gub")]
+        cur = self._enter(*objs, *outs.values())
+        check(lib().pdplqr_admm_project_vjp(self.h, *[p[0] for p in ps], *po, mem))
+        self._leave(cur)
+        return outs
+
+    def admm_adjoint_fixed_point(self, ws, ys, zs, lb, ub, rho, gws, sigma, alpha, tol=1e-8, max_iter=4000,
+                                 check_every=25, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, glb=None,
+                                 gub=None):
+        """Gradients of the ADMM fixed point ``(ws, ys, zs)`` the handle last
+        factored the x-update at, by the fixed-point adjoint iterated on the
+        device (include/pdplqr.h: pdplqr_admm_adjoint_fixed_point): box rows
+        and the handle's cones alike.  ``ws`` is that x-update's ``forward``
+        result, ``gws`` = d loss / d ws; outputs left ``None`` are not
+        computed.  ``admm_adjoint_fixed_point_info()`` tells how it ended."""
+        objs = [ws, ys, zs, lb, ub, rho, gws, gE, gc, gH, gh, gx, gD, glb, gub]
+        names = ("ws", "ys", "zs", "lb", "ub", "rho", "gws", "gE", "gc", "gH", "gh", "gx", "gD", "glb", "gub")
+        ps = [_ptr(o, nm) for o, nm in zip(objs, names)]
+        cur = self._enter(*objs)
+        check(lib().pdplqr_admm_adjoint_fixed_point(self.h, *[p[0] for p in ps[:7]], float(sigma), float(alpha),
+                                                    float(tol), int(max_iter), int(check_every),
+                                                    *[p[0] for p in ps[7:]], _mem_of(*ps)))
+        self._leave(cur)
+
+    def admm_adjoint_fixed_point_info(self):
+        """The last ``admm_adjoint_fixed_point``, per problem: ``iters`` (the
+        iteration of its last test), ``converged`` and ``resid`` [batch][2]:
+        the max-norm change and the max-norm of the adjoint state there."""
+        it = np.zeros(self.batch, dtype=np.int32)
+        cv = np.zeros(self.batch, dtype=np.int32)
+        rs = np.zeros((self.batch, 2))
+        i32 = C.POINTER(C.c_int32)
+        check(lib().pdplqr_admm_adjoint_fixed_point_info(self.h, it.ctypes.data_as(i32), cv.ctypes.data_as(i32),
+                                                         C.c_void_p(rs.ctypes.data)))
+        return {"iters": it, "converged": cv.astype(bool), "resid": rs}
+
     def set_infeasibility_detection(self, enable: bool, eps_prim_inf: float = 1e-4, eps_dual_inf: float = 1e-4):
         """Switch OSQP's infeasibility certificates of ``admm_solve`` on or off
         (include/pdplqr.h: pdplqr_admm_set_infeasibility_detection)."""
@@ -725,6 +776,22 @@ class BatchedLQRSolver:
         """The projection of ``v [batch][ny]`` onto the constraint set (boxes
         and cones); see pdplqr_admm_project."""
         return self._hd.project(v, lb, ub)
+
+    def project_vjp(self, v, lb, ub, gout, want=("gv", "glb", "gub")):
+        """The projection's transposed Jacobian at ``v`` applied to ``gout``;
+        see pdplqr_admm_project_vjp."""
+        return self._hd.project_vjp(v, lb, ub, gout, want)
+
+    def admm_adjoint_fixed_point(self, ws, ys, zs, lb, ub, rho, gws, sigma, alpha, tol=1e-8, max_iter=4000,
+                                 check_every=25, gE=None, gc=None, gH=None, gh=None, gx=None, gD=None, glb=None,
+                                 gub=None):
+        """The fixed-point adjoint of the ADMM loop at its solution, box and
+        cone rows alike; see pdplqr_admm_adjoint_fixed_point."""
+        self._hd.admm_adjoint_fixed_point(ws, ys, zs, lb, ub, rho, gws, sigma, alpha, tol, max_iter, check_every,
+                                          gE, gc, gH, gh, gx, gD, glb, gub)
+
+    def admm_adjoint_fixed_point_info(self):
+        return self._hd.admm_adjoint_fixed_point_info()
 
     def value_function(self, b, k):
         return self._hd.value_function(b, k)
